@@ -20,6 +20,14 @@ kernel from the committed rocprofv3 PMC summary (profiles/pmc_*.json, FETCH_SIZE
 cpu_baseline: the C restatement (oracle/, kind "port") on this host's cores, same config and actions,
 bounded sample.
 
+A plain run does only what the headline needs: set up, warm up, time --steps steps, write --dump-outputs, print
+the line (with the roofline figures that come from the timed region's own HIP events). --full adds every measurement
+that takes a run of its own: the other obs dtype, the packed-obs lines, the measured HBM copy peak and the CPU baseline
+(--alt-steps, --packed-steps, --cpu-seconds and --no-cpu-baseline shape those and mean nothing without --full).
+--dump-outputs DIR writes what the last timed step returned to a caller (obs, reward, done, ev_act, ev_watch, ev_misc
+of a fixed seeded sample of envs, plus env_index) as DIR/<name>.npy; the inputs are seeded, so two builds run with the
+same arguments can be compared array for array.
+
 Multi-GPU (weak scaling, env ranges sharded, no collective in the data path): either the driver's
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`, or plain `python bench.py --gpus N`,
 which starts the N rank processes itself (launch_ranks) before anything touches the GPU and prints rank 0's
@@ -181,6 +189,31 @@ def stream_copy_gbs(dev, nbytes=2 << 30, reps=10):
     del a, b
     torch.cuda.empty_cache()
     return res
+
+
+DUMP_OBS_BYTES = 48 * 10 ** 6  # obs share of the --dump-outputs budget (64 MB in all; the other arrays are small)
+
+
+def dump_outputs(out_dir, arrays, B, rank, world):
+    """Write the last timed step's outputs of a fixed sample of envs as <name>.npy (float32 / float64).
+    arrays: {name: device tensor [B, ...]}. The sample is every env when the obs fit DUMP_OBS_BYTES, else a sorted
+    draw without replacement from default_rng(0); env_index.npy holds it. Ranks of a multi-GPU run add _rank<r>."""
+    import numpy as np
+    import torch
+    obs = arrays['obs']
+    per_env = obs[0].numel() * obs.element_size()
+    n = min(B, max(1, DUMP_OBS_BYTES // per_env))
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+    idx_t = torch.from_numpy(idx).to(obs.device)
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    sfx = f'_rank{rank}' if world > 1 else ''
+    np.save(out_dir / f'env_index{sfx}.npy', idx.astype(np.float64))
+    for name, t in arrays.items():
+        a = t.index_select(0, idx_t).cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64 if a.dtype.itemsize >= 4 else np.float32)  # exact for u8 and i32
+        np.save(out_dir / f'{name}{sfx}.npy', a)
 
 
 def load_pmc(workload):
@@ -372,6 +405,12 @@ def main():
     ap.add_argument('--serial', action='store_true',
                     help='attribution run: every kernel on one stream (mfg_variant.serial), so per-kernel times '
                          'exclude the second stream\'s overlap (C4); not a headline line')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the side measurements: the other obs dtype, packed obs, the HBM copy peak and the '
+                         'CPU baseline (a plain run times the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the last timed step\'s outputs (a fixed seeded sample of envs) '
+                         'as DIR/<name>.npy')
     ap.add_argument('--dry-run', action='store_true',
                     help='CPU rehearsal of the rank protocol (gloo, no GPU, no engine); not a bench number')
     args = ap.parse_args()
@@ -404,6 +443,7 @@ def main():
     eng.reset(obs=obs[0], init=True, seed_base=env_base)
     stream = torch.cuda.current_stream(dev)
     step_no = 0
+    last_k = 0  # steps of the latest mfg_step call: its step last_k - 1 is the latest step's row of every buffer
     red_dev = dev if backend in (None, 'nccl') else torch.device('cpu')  # gloo reduces host tensors
     episodes = torch.zeros((), dtype=torch.float64, device=red_dev)
 
@@ -411,7 +451,7 @@ def main():
         """n steps in calls of F (the last call may be shorter). Per-kernel HIP events are recorded only
         around full-K calls, so the per-launch roofline figures are always those of K=F launches.
         after(k): work run on the stream after each call (the dense obs consumer of the packed comparison)."""
-        nonlocal step_no
+        nonlocal step_no, last_k
         done_steps = 0
         while done_steps < n:
             k = min(F, n - done_steps)
@@ -429,6 +469,7 @@ def main():
                 e.record(stream)
                 events.append((s, e, k))
             step_no += k
+            last_k = k
             done_steps += k
 
     run(args.warmup)
@@ -455,6 +496,11 @@ def main():
         dist.all_reduce(episodes)  # optional metrics all-reduce (tiny, latency-bound)
     total = B * world * args.steps
     value = total / elapsed
+    if args.dump_outputs:
+        j = last_k - 1
+        dump_outputs(args.dump_outputs, {'obs': obs[j], 'reward': rew[j], 'done': done[j], 'ev_act': ev_a[j],
+                                         'ev_watch': ev_w[j], 'ev_misc': ev_m[j]}, B, rank, world)
+
     def timed(n, obs_buf, after=None):
         """n more steps into obs_buf, timed like the headline (barrier + synchronize brackets, max over ranks)."""
         run(F, obs_buf=obs_buf, after=after)
@@ -477,7 +523,7 @@ def main():
 
     # the same workload with the other obs precision (the reference's own obs are f64, Q25), timed the same way
     alt = None
-    alt_steps = args.steps if args.alt_steps is None else args.alt_steps
+    alt_steps = 0 if not args.full else args.steps if args.alt_steps is None else args.alt_steps
     if alt_steps > 0:
         alt_dtype = 'f32' if args.obs_dtype == 'f64' else 'f64'
         obs_alt = torch.zeros((F,) + eng.obs_shape(), dtype=torch.float64 if alt_dtype == 'f64' else torch.float32,
@@ -494,7 +540,7 @@ def main():
     # packed obs: the nonzero entries per agent row instead of the dense obs; beside it the same
     # with the policy-input projection fused into the render, and what that replaces (dense obs + one GEMM)
     packed = None
-    packed_steps = args.steps if args.packed_steps is None else args.packed_steps
+    packed_steps = 0 if not args.full else args.steps if args.packed_steps is None else args.packed_steps
     if packed_steps > 0:
         from mfg_amd.engine import PackedObs
         kdim = eng.lmax * eng.obs_hw[0] * eng.obs_hw[1]
@@ -617,20 +663,22 @@ def main():
             roof = {"bound": "hbm", "achieved": round(pipe_bytes / mean_call / 1e9, 2), "peak": HBM_PEAK_GBS,
                     "unit": "GB/s", "frac": round(pipe_bytes / mean_call / 1e9 / HBM_PEAK_GBS, 5),
                     "traffic": None, "kernel": "mfg_step pipeline", "mean_launch_ms": round(mean_call * 1e3, 3)}
-        try:
-            copies = stream_copy_gbs(dev)
-        except RuntimeError:  # not enough free HBM for the 4 GiB copy pair
-            copies = {}
-        peak_meas = copies.get('hip_copy16')
-        roof["peak_measured"] = peak_meas
-        roof["peak_measured_how"] = ("hand-written 16-B-per-lane HIP copy kernel (mfg_hbm_copy) over 2 GiB, 2 x 2 GiB "
-                                     f"moved, best of 10; torch copy_ of the same buffers: {copies.get('torch_copy_')} GB/s")
-        if peak_meas and roof.get("achieved"):
-            roof["frac_of_measured"] = round(roof["achieved"] / peak_meas, 5)
-        if peak_meas and roof.get("pipeline"):
-            roof["pipeline"]["frac_of_measured"] = round(roof["pipeline"]["achieved"] / peak_meas, 5)
+        if args.full:
+            try:
+                copies = stream_copy_gbs(dev)
+            except RuntimeError:  # not enough free HBM for the 4 GiB copy pair
+                copies = {}
+            peak_meas = copies.get('hip_copy16')
+            roof["peak_measured"] = peak_meas
+            roof["peak_measured_how"] = ("hand-written 16-B-per-lane HIP copy kernel (mfg_hbm_copy) over 2 GiB, 2 x 2 "
+                                         "GiB moved, best of 10; torch copy_ of the same buffers: "
+                                         f"{copies.get('torch_copy_')} GB/s")
+            if peak_meas and roof.get("achieved"):
+                roof["frac_of_measured"] = round(roof["achieved"] / peak_meas, 5)
+            if peak_meas and roof.get("pipeline"):
+                roof["pipeline"]["frac_of_measured"] = round(roof["pipeline"]["achieved"] / peak_meas, 5)
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             visible = len(os.sched_getaffinity(0))
             quota = cgroup_cpus()
             usable = min(visible, quota) if quota else visible
@@ -647,7 +695,8 @@ def main():
         out = {
             "metric": METRIC, "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world,
             **rank_fields(n_ranks, backend),
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "steps": args.steps, "warmup": args.warmup, "full": args.full,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": f"f64 rewards/battery/dirt, {args.obs_dtype} obs",
             "data": "synthetic (Philox4x32-10 uniform random actions, device-side)",

@@ -98,13 +98,13 @@ def test_bench_launcher_two_ranks_share_gpu(tmp_path):
 
 
 def test_bench_default_lines_run(tmp_path):
-    """bench.py with its default lines (f64 headline, the other obs dtype, packed entries, fused projection,
+    """bench.py --full with its default lines (f64 headline, the other obs dtype, packed entries, fused projection,
     dense f32 + projection GEMM, CPU baseline) on a small batch: the run the driver makes, shortened. Every side
     line must be present and positive (a dtype mismatch in one of them once crashed the default run)."""
     if not gpu_available():
         pytest.skip('no GPU')
-    r = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--batch', '4096', '--warmup', '16', '--steps', '32',
-                        '--cpu-seconds', '1'], capture_output=True, text=True, timeout=500)
+    r = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--full', '--batch', '4096', '--warmup', '16',
+                        '--steps', '32', '--cpu-seconds', '1'], capture_output=True, text=True, timeout=500)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
     assert line['value'] > 0 and 'f64 obs' in line['dtype']
@@ -115,6 +115,53 @@ def test_bench_default_lines_run(tmp_path):
     assert line['roofline']['frac'] > 0 and 'frac_sec8d' not in line['roofline'] and line['parity']['timed_mode_test']
     assert line['roofline']['peak_measured'] > 1000  # the HIP copy kernel's GB/s
     assert line['backend'] is None and line['n_ranks_rccl'] is None  # bare single process: no group
+
+
+def test_bench_plain_run_is_lean_and_dumps_last_step(tmp_path):
+    """A plain bench.py run (no --full) times the headline only: no side line, no copy peak, no CPU baseline. Its
+    --dump-outputs arrays are float32 / float64 and equal, bit for bit, the last step of an engine stepped here over
+    the same envs with the bench's seeds: 20 = 8 warm-up + 12 timed steps, the last call a short one (K = 4)."""
+    if not gpu_available():
+        pytest.skip('no GPU')
+    B, K, warm, steps = 256, 8, 8, 12
+    r = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--gpus', '1', '--batch', str(B), '--warmup',
+                        str(warm), '--steps', str(steps), '--dump-outputs', str(tmp_path / 'dump')],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
+    assert line['value'] > 0 and line['steps'] == steps and line['ms_per_step'] > 0 and line['full'] is False
+    # value = envs / seconds per step (ms_per_step is rounded to 1e-4 ms: 1% of a 0.01-ms step at the worst)
+    assert abs(line['value'] * line['ms_per_step'] * 1e-3 / B - 1) < 1e-2
+    assert line['alt_obs_dtype'] is None and line['packed_obs'] is None and line['cpu_baseline'] is None
+    assert 'peak_measured' not in line['roofline']
+    got = {p.stem: np.load(p) for p in (tmp_path / 'dump').glob('*.npy')}
+    assert set(got) == {'env_index', 'obs', 'reward', 'done', 'ev_act', 'ev_watch', 'ev_misc'}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got['env_index'], np.arange(B))  # 256 envs of obs fit the budget: no sampling
+
+    import torch
+    from mfg_amd.engine import EV_MISC, Engine
+    from mfg_amd.spec import compile_spec
+    spec = compile_spec('large8.yaml')
+    eng = Engine(spec, B, device=0)
+    dev, A = eng.device, spec.n_agents
+    buf = dict(obs=torch.zeros((K,) + eng.obs_shape(), dtype=torch.float64, device=dev),
+               reward=torch.zeros((K, B, A), dtype=torch.float64, device=dev),
+               done=torch.zeros((K, B), dtype=torch.uint8, device=dev),
+               ev_act=torch.zeros((K, B, A), dtype=torch.uint8, device=dev),
+               ev_watch=torch.zeros((K, B, A), dtype=torch.uint8, device=dev),
+               ev_misc=torch.zeros((K, B, EV_MISC), dtype=torch.int32, device=dev))
+    eng.reset(obs=buf['obs'][0], init=True, seed_base=0)
+    t = 0
+    for k in (8, 8, 4):  # warm-up call, then the timed calls of 8 and 4 steps
+        eng.step(k, actions=None, philox_seed=12345, env_base=0, step_base=t, auto_reset=True, **buf)
+        t += k
+    for name, b in buf.items():
+        want = b[k - 1].cpu().numpy()
+        assert got[name].shape == want.shape, name
+        assert np.array_equal(got[name], want.astype(got[name].dtype)), name
+    assert got['obs'].dtype == np.float64 and np.abs(got['obs']).sum() > 0
+    eng.close()
 
 
 @pytest.mark.timeout(600)

@@ -146,3 +146,43 @@ def test_bench_under_launcher_world1_joins_a_group():
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{')][-1])
     assert d['backend'] == 'gloo' and d['n_ranks_gloo'] == 1 and d['n_gpus'] == 1
     assert d['metrics_allreduce'] == 8 * 3
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_float(tmp_path, monkeypatch):
+    """bench.dump_outputs on host tensors: every array is written as float32 / float64 with its values unchanged,
+    all envs when the obs fit the byte budget, else one fixed sorted sample (the same on every call) of as many
+    envs as fit, with env_index naming them; ranks of a multi-GPU run write under their own names."""
+    import sys
+    import torch
+    sys.path.insert(0, str(ROOT))
+    try:
+        import bench
+    finally:
+        sys.path.remove(str(ROOT))
+    B = 37
+    g = torch.Generator().manual_seed(3)
+    arrays = {'obs': torch.rand((B, 2, 3, 3), generator=g, dtype=torch.float64),
+              'reward': torch.rand((B, 2), generator=g, dtype=torch.float64),
+              'done': torch.randint(0, 2, (B,), generator=g, dtype=torch.uint8),
+              'ev_misc': torch.randint(-2 ** 31, 2 ** 31 - 1, (B, 4), generator=g, dtype=torch.int32)}
+    bench.dump_outputs(tmp_path / 'all', arrays, B, 0, 1)
+    got = {p.stem: np.load(p) for p in (tmp_path / 'all').glob('*.npy')}
+    assert set(got) == set(arrays) | {'env_index'}
+    assert np.array_equal(got['env_index'], np.arange(B))
+    for name, t in arrays.items():
+        assert got[name].dtype in (np.float32, np.float64), name
+        assert np.array_equal(got[name].astype(t.numpy().dtype), t.numpy()), name
+    assert got['obs'].dtype == np.float64 and got['ev_misc'].dtype == np.float64 and got['done'].dtype == np.float32
+
+    monkeypatch.setattr(bench, 'DUMP_OBS_BYTES', 10 * 2 * 3 * 3 * 8 + 5)  # room for 10 envs of obs
+    for d in ('a', 'b'):
+        bench.dump_outputs(tmp_path / d, arrays, B, 1, 2)
+    a = {p.stem: np.load(p) for p in (tmp_path / 'a').glob('*.npy')}
+    b = {p.stem: np.load(p) for p in (tmp_path / 'b').glob('*.npy')}
+    assert set(a) == {f'{n}_rank1' for n in got}
+    idx = a['env_index_rank1'].astype(np.int64)
+    assert len(idx) == 10 and len(set(idx)) == 10 and (np.diff(idx) > 0).all() and 0 <= idx[0] and idx[-1] < B
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name
+    assert np.array_equal(a['obs_rank1'], arrays['obs'].numpy()[idx])
+    assert np.array_equal(a['ev_misc_rank1'], arrays['ev_misc'].numpy()[idx].astype(np.float64))

@@ -11,8 +11,10 @@ if [ "$PART" = A ]; then
   tail -1 gpurun_out/${T}_gpu_tests.txt
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${T}_smoke.txt 2>&1 || { tail -20 gpurun_out/${T}_smoke.txt; exit 1; }
   tail -2 gpurun_out/${T}_smoke.txt
-  timeout -k 10 400 python bench.py > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err || { tail -20 gpurun_out/${T}_bench.err; exit 1; }
-  python -c "import json; d=json.load(open('gpurun_out/${T}_bench.json')); print(d['value'], d['ms_per_step'], d['roofline']['kernel'], d['roofline']['frac'], d['cpu_baseline'])"
+  # the full line (side lines, copy peak, CPU baseline): bench.py --full; kept in bench_out/
+  mkdir -p bench_out
+  timeout -k 10 400 python bench.py --full > bench_out/${T}_bench.json 2> bench_out/${T}_bench.err || { tail -20 bench_out/${T}_bench.err; exit 1; }
+  python -c "import json; d=json.load(open('bench_out/${T}_bench.json')); print(d['value'], d['ms_per_step'], d['roofline']['kernel'], d['roofline']['frac'], d['cpu_baseline'])"
 else
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/${T}_prof -o run -- python3 bench.py --no-cpu-baseline --steps 200 --warmup 50 > gpurun_out/${T}_prof.log 2>&1 \
     || { tail -20 gpurun_out/${T}_prof.log; exit 1; }
