@@ -31,6 +31,7 @@ extern "C" {
 #define MFG_MAX_COMBINED 144  /* members of one Combined layer: every other agent (Other) + the entity tags */
 #define MFG_MAX_RULES 32
 #define MFG_MAX_DOORS 128   /* doors > 64: the same two-pass kernels (the reference large_qquad level has 65) */
+#define MFG_MAX_GROUP 128   /* items, charge pods, drop-off locations, destinations per env: the same two passes above 64 */
 #define MFG_MAX_POSITIONS 64  /* configured spawn / destination cells per agent */
 
 /* ---- action opcodes (reference: environment/actions.py, modules/<m>/actions.py) ---- */

@@ -354,7 +354,7 @@ static int create_impl(const mfg_spec* s, int device, int64_t n_envs, const mfg_
   h.dd = h.oh * h.ow;
   h.fr = std::min(h.oh, h.ow);
   h.nrays = s->n_rays;
-  h.lane_passes = (s->n_agents > MFG_WAVE || s->n_doors > MFG_WAVE) ? 2 : 1;
+  h.lane_passes = (s->n_agents > MFG_WAVE || s->n_doors > MFG_WAVE) ? 2 : 1;  // (or a group above 64 slots, below)
   for (int a = 0; a < s->n_agents; a++) {  // combined layers that are plain member counts (MfgDevSpec)
     uint32_t tm = 0;
     uint64_t am[2] = {0, 0};
@@ -388,7 +388,7 @@ static int create_impl(const mfg_spec* s, int device, int64_t n_envs, const mfg_
     // per-agent tables live in HBM pool slots, so they do not cost the other renders' occupancy)
     if (s->n_agents <= MFG_WAVE)
       for (int k : SIZES) if (k >= mp) { h.maxpts = k; break; }
-    h.lrpts = h.maxpts ? 0 : align_up(mp, 32);
+    h.lrpts = align_up(mp, 32);  // (cleared below when a k_obs<MAXPTS> instantiation renders the spec)
   }
   int lmax = 1;
   for (int a = 0; a < s->n_agents; a++) lmax = s->n_layers[a] > lmax ? s->n_layers[a] : lmax;
@@ -407,9 +407,27 @@ static int create_impl(const mfg_spec* s, int device, int64_t n_envs, const mfg_
     if (ru.op == MFG_RULE_SPAWN_MAINTAINERS) kmax = ru.i[0];
     if (ru.op == MFG_RULE_MOVE_MAINTAINERS) moving = 1;
   }
-  if (imax > 64 || pmax > 64 || dropmax > 64 || destmax > 64 || mmax > 30 || kmax > 64) {
-    delete e; return fail("group quantity too large for the engine");
+  {
+    const struct { const char* name; int n, cap; } caps[] = {
+        {"Items", imax, MFG_MAX_GROUP},         {"ChargePods", pmax, MFG_MAX_GROUP},
+        {"DropOffLocations", dropmax, MFG_MAX_GROUP}, {"Destinations", destmax, MFG_MAX_GROUP},
+        {"Machines", mmax, 30},                 {"Maintainers", kmax, MFG_WAVE}};
+    for (const auto& c : caps)
+      if (c.n > c.cap) {
+        delete e;
+        return fail(std::string("group quantity too large for the engine: ") + c.name + " " + std::to_string(c.n) +
+                    " > " + std::to_string(c.cap));
+      }
+    // SpawnDestinationsPerAgent tests its candidate cells against one 64-slot pass of destinations
+    if (s->n_dest_entries > MFG_WAVE) { delete e; return fail("SpawnDestinationsPerAgent with more than 64 entries"); }
   }
+  // a group above 64 slots: the two-pass step and reset kernels (each pass holds 64 slots, as for agents and doors) and
+  // the long-ray render, the one render compiled with the second word of the identifier-dedupe suppression sets
+  if (std::max(std::max(imax, pmax), std::max(dropmax, destmax)) > MFG_WAVE) {
+    h.lane_passes = 2;
+    h.maxpts = 0;
+  }
+  if (h.maxpts) h.lrpts = 0;
   h.imax = imax; h.pmax = pmax; h.dropmax = dropmax; h.destmax = destmax; h.mmax = mmax; h.kmax = kmax;
   h.mstate_ints = MS_NEXT + mmax + 1;
   h.path_cap = moving ? std::min(std::min(4 * (s->H + s->W), s->n_floor), 1000) : 0;  // route fits the 2 KB scratch

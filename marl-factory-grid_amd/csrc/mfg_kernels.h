@@ -768,6 +768,28 @@ __device__ __forceinline__ int grp_count(const int* tbl, int n, int cell, int ne
   for (int b = 0; b < n; b += MFG_WAVE) c += popc(grp_at(tbl + b, n - b, cell, need, lane));
   return c;
 }
+// items, charge pods, drop-offs and destinations: up to GW * 64 slots, 64 per pass, unrolled (GW is the kernel's NW:
+// MfgDevSpec::lane_passes is 2 when one of these groups has more than 64 slots). Lowest matching slot, or -1.
+template <int GW>
+__device__ __forceinline__ int grp_first_g(const int* tbl, int n, int cell, int need, int lane) {
+#pragma unroll
+  for (int g = 0; g < GW; g++) {
+    const u64 m = grp_at(tbl + g * MFG_WAVE, n - g * MFG_WAVE, cell, need, lane);
+    if (m) return g * MFG_WAVE + ffs64(m);
+  }
+  return -1;
+}
+// the present slot at `cell` whose identifier base + slot equals `id`, or -1
+template <int GW>
+__device__ __forceinline__ int grp_id_at(const int* tbl, int n, int cell, int base, int id, int lane) {
+#pragma unroll
+  for (int g = 0; g < GW; g++) {
+    const u64 m = grp_at(tbl + g * MFG_WAVE, n - g * MFG_WAVE, cell, EW_PRESENT, lane) &
+                  ballot(base + g * MFG_WAVE + lane == id);
+    if (m) return g * MFG_WAVE + ffs64(m);
+  }
+  return -1;
+}
 // Agent- and door-parallel code runs NW passes of 64 lanes (NW = 2: specs with more than 64 agents or doors); in pass h
 // lane l holds agent / door h * 64 + l. NW is a template parameter of the step and reset kernels
 // (MfgDevSpec::lane_passes).
@@ -790,23 +812,21 @@ __device__ __forceinline__ int door_idx(const Env& e, int cell) {
 }
 // the present int-identifier entity at `cell` whose identifier equals `id` (at most one, pos_dict keeps
 // identifiers unique per cell); returns its kind, *slot = group slot
+template <int GW>
 __device__ int find_present_id(const Env& e, int cell, int id, int* slot) {
   const int lane = e.lane;
   int d = door_idx(e, cell);
   if (d >= 0 && d == id && (e.door()[d] & DW_PRESENT)) { *slot = d; return K_DOOR; }
   u64 m;
-  int base = e.H(H_ITEM_BASE);
-  m = grp_at(e.items(), e.H(H_N_ITEMS), cell, EW_PRESENT, lane) & ballot(base + lane == id);
-  if (m) { *slot = ffs64(m); return K_ITEM; }
-  base = e.H(H_POD_BASE);
-  m = grp_at(e.pods(), e.H(H_N_PODS), cell, EW_PRESENT, lane) & ballot(base + lane == id);
-  if (m) { *slot = ffs64(m); return K_POD; }
-  base = e.H(H_DROP_BASE);
-  m = grp_at(e.drops(), e.H(H_N_DROPS), cell, EW_PRESENT, lane) & ballot(base + lane == id);
-  if (m) { *slot = ffs64(m); return K_DROP; }
-  base = e.H(H_DEST_BASE);
-  m = grp_at(e.dests(), e.H(H_N_DESTS), cell, EW_PRESENT, lane) & ballot(base + lane == id);
-  if (m) { *slot = ffs64(m); return K_DEST; }
+  int base, k;
+  k = grp_id_at<GW>(e.items(), e.H(H_N_ITEMS), cell, e.H(H_ITEM_BASE), id, lane);
+  if (k >= 0) { *slot = k; return K_ITEM; }
+  k = grp_id_at<GW>(e.pods(), e.H(H_N_PODS), cell, e.H(H_POD_BASE), id, lane);
+  if (k >= 0) { *slot = k; return K_POD; }
+  k = grp_id_at<GW>(e.drops(), e.H(H_N_DROPS), cell, e.H(H_DROP_BASE), id, lane);
+  if (k >= 0) { *slot = k; return K_DROP; }
+  k = grp_id_at<GW>(e.dests(), e.H(H_N_DESTS), cell, e.H(H_DEST_BASE), id, lane);
+  if (k >= 0) { *slot = k; return K_DEST; }
   const int nd = e.H(H_N_DIRT);
   for (int b = 0; b < nd; b += MFG_WAVE) {
     const int i = b + lane;
@@ -826,9 +846,10 @@ __device__ int find_present_id(const Env& e, int cell, int id, int* slot) {
   return K_NONE;
 }
 // Objects.notify_del_entity x2 on the global pos_dict: list.remove() drops the first identifier-equal entry
+template <int GW>
 __device__ void global_remove_id(const Env& e, int cell, int id) {
   int slot;
-  int k = find_present_id(e, cell, id, &slot);
+  int k = find_present_id<GW>(e, cell, id, &slot);
   if (e.lane == 0) {
     switch (k) {
       case K_DOOR: e.door()[slot] &= ~DW_PRESENT; break;
@@ -967,11 +988,12 @@ __device__ int spawn_positions(const Env& e, int n, int ignore_blocking, int* ou
 // ------------------------------------------------------------------------------------------------
 // append one int-id entity to a group table; it enters the global pos_dict only if no entity with an
 // equal identifier is already there (Objects.notify_add_entity, objects.py:203-214)
+template <int GW>
 __device__ void spawn_into(const Env& e, int* tbl, int hn, int base, int cell, int extra = 0) {
   int n = e.H(hn);
   int slot;
   int id = base + n;
-  bool present = find_present_id(e, cell, id, &slot) == K_NONE;
+  bool present = find_present_id<GW>(e, cell, id, &slot) == K_NONE;
   if (e.lane == 0) tbl[n] = cell | EW_ALIVE | (present ? EW_PRESENT : 0) | extra;
   e.setH(hn, n + 1);
   wave_sync();
@@ -987,6 +1009,7 @@ __device__ double dirt_global_amount(const Env& e) {  // clean_up/groups.py:27-3
 #define DIRTPILE_MAX_LOCAL 5.0  /* DirtPile(max_local_amount=5): the collection value is never forwarded (Q20) */
 
 // DirtPiles.trigger_spawn (clean_up/groups.py:70-95); returns spawn_counter, *valid = result validity
+template <int GW>
 __device__ int dirt_trigger_spawn(const Env& e, int q, double amount, int* valid, int* scratch) {
   const CS mfg_spec& s = e.S->s;
   double u = pcg_uniform(e, -s.dirt_n_var, s.dirt_n_var);
@@ -1021,7 +1044,7 @@ __device__ int dirt_trigger_spawn(const Env& e, int q, double amount, int* valid
       if (nd >= e.S->dirt_cap) { e.setH(H_OVERFLOW, 1); *valid = 0; return counter; }
       int id = e.H(H_CNT_DIRT);
       int slot;
-      bool present = find_present_id(e, cell, id, &slot) == K_NONE;
+      bool present = find_present_id<GW>(e, cell, id, &slot) == K_NONE;
       if (e.lane == 0) {
         e.dirtpos()[nd] = cell | EW_ALIVE | (present ? EW_PRESENT : 0);
         e.dirtid()[nd] = id;
@@ -1039,11 +1062,12 @@ __device__ int dirt_trigger_spawn(const Env& e, int q, double amount, int* valid
 }
 
 // remove dirt slot k keeping collection order (Collection.__delitem__)
+template <int GW>
 __device__ void dirt_delete(const Env& e, int k) {
   const int nd = e.H(H_N_DIRT);
   const int cell = EW_POS(e.dirtpos()[k]);
   const int id = e.dirtid()[k];
-  global_remove_id(e, cell, id);
+  global_remove_id<GW>(e, cell, id);
   for (int b = k & ~(MFG_WAVE - 1); b < nd; b += MFG_WAVE) {  // shift slots k+1.. down by one, 64 per pass
     const int j = b + e.lane;
     const bool mv = j > k && j < nd;
@@ -1199,21 +1223,20 @@ __device__ void do_action(const Env& e, StepOut<NW>& o, int a, int slot) {
   } else if (op == MFG_ACT_DOORUSE) {  // doors/actions.py:18-34
     valid = door_use_at<NW>(e, x, y);
   } else if (op == MFG_ACT_ITEM) {  // items/actions.py:41-63
-    if (grp_at(e.drops(), e.H(H_N_DROPS), pos, EW_ALIVE, e.lane)) {
+    if (grp_first_g<NW>(e.drops(), e.H(H_N_DROPS), pos, EW_ALIVE, e.lane) >= 0) {
       valid = 0;  // inventories are always empty (pickup bug, Q8)
       aux = 1;
     } else {
-      u64 m = grp_at(e.items(), e.H(H_N_ITEMS), pos, EW_ALIVE, e.lane);
-      if (m) {
-        const int k = ffs64(m);
-        global_remove_id(e, pos, e.H(H_ITEM_BASE) + k);
+      const int k = grp_first_g<NW>(e.items(), e.H(H_N_ITEMS), pos, EW_ALIVE, e.lane);
+      if (k >= 0) {
+        global_remove_id<NW>(e, pos, e.H(H_ITEM_BASE) + k);
         if (e.lane == 0) e.items()[k] = (e.items()[k] & ~0xFFFF) | EW_NOPOS;
         wave_sync();
         valid = 1;
       }
     }
   } else if (op == MFG_ACT_CHARGE) {  // batteries/actions.py:20-31, entitites.py:98-111
-    if (grp_at(e.pods(), e.H(H_N_PODS), pos, EW_ALIVE, e.lane)) {
+    if (grp_first_g<NW>(e.pods(), e.H(H_N_PODS), pos, EW_ALIVE, e.lane) >= 0) {
       const double ch = e.bat()[a];
       if (ch >= 1.0) valid = 0;
       else if (agents_count_at<NW>(e, pos) > 1) valid = 0;
@@ -1230,7 +1253,7 @@ __device__ void do_action(const Env& e, StepOut<NW>& o, int a, int slot) {
     if (k >= 0) {
       const double na = e.dirtamt()[k] - S->s.dirt_clean_amount;
       if (na <= 0) {
-        dirt_delete(e, k);
+        dirt_delete<NW>(e, k);
       } else {
         wave_sync();
         if (e.lane == 0) {
@@ -1242,7 +1265,7 @@ __device__ void do_action(const Env& e, StepOut<NW>& o, int a, int slot) {
       valid = 1;
     }
   } else if (op == MFG_ACT_DEST) {  // destinations/actions.py:17-24
-    if (grp_at(e.dests(), e.H(H_N_DESTS), pos, EW_ALIVE, e.lane)) {
+    if (grp_first_g<NW>(e.dests(), e.H(H_N_DESTS), pos, EW_ALIVE, e.lane) >= 0) {
       o.crashed = 1;  // AttributeError upstream (Q17)
       return;
     }
@@ -1668,12 +1691,13 @@ __device__ bool maint_route(const Env& e, int k, int target_cell, int* crashed) 
   return true;
 }
 // Entity.move of maintainer k to `cell` (entity.py:175-199): global pos_dict by identifier (Q14)
+template <int GW>
 __device__ void maint_move(const Env& e, int k, int cell) {
   const int id = e.H(H_MAINT_BASE) + k;
   const int old = EW_POS(uni(e.maints()[k]));
-  global_remove_id(e, old, id);
+  global_remove_id<GW>(e, old, id);
   int slot;
-  const bool present = find_present_id(e, cell, id, &slot) == K_NONE;
+  const bool present = find_present_id<GW>(e, cell, id, &slot) == K_NONE;
   wave_sync();
   if (e.lane == 0) e.maints()[k] = cell | EW_ALIVE | (present ? EW_PRESENT : 0);
   wave_sync();
@@ -1749,7 +1773,7 @@ __device__ void maint_tick(const Env& e, int k, int* crashed) {
   int debt = 1;
   if (S->level[nxt] != 1) {
     debt++;
-    maint_move(e, k, nxt);
+    maint_move<NW>(e, k, nxt);
   }
   e.setH(H_DEBT, e.H(H_DEBT) + debt);
   wave_sync();
@@ -1817,7 +1841,7 @@ __device__ void rule_tick_step(const Env& e, StepOut<NW>& o, int ri, int* scratc
     if (c < 0) {
     } else if (!c) {
       int valid = 0, v = 0;
-      if constexpr (RNG) v = dirt_trigger_spawn(e, ru.i[1], ru.f[0], &valid, scratch);
+      if constexpr (RNG) v = dirt_trigger_spawn<NW>(e, ru.i[1], ru.f[0], &valid, scratch);
       else o.crashed = 1;  // unreachable: the host stages the full record for specs with RespawnDirt
       o.dirt_spawn_value = v;
       o.dirt_spawn_valid = valid;
@@ -2038,15 +2062,21 @@ __device__ void rule_check_done(const Env& e, StepOut<NW>& o, int ri) {
     if (e.H(H_N_DIRT) == 0 && e.H(H_STEP)) { o.done = 1; o.done_mask |= 1 << ri; o.g_rew += ru.f[0]; }
   } else if (op == MFG_RULE_DONE_DEST) {  // destinations/rules.py:73-92
     const int n = e.H(H_N_DESTS);
-    const bool rr = e.lane < n && (e.dests()[e.lane < n ? e.lane : 0] & EW_REACHED);
-    const u64 m = ballot(rr);
-    const bool any = m != 0, all = popc(m) == n;
+    int nr = 0;
+#pragma unroll
+    for (int h = 0; h < NW; h++) {
+      const int i = h * MFG_WAVE + e.lane;
+      nr += popc(ballot(i < n && (e.dests()[i < n ? i : 0] & EW_REACHED)));
+    }
+    const bool any = nr != 0, all = nr == n;
     const int cond = ru.i[0];
     if ((cond == MFG_DEST_ANY && any) || (cond != MFG_DEST_ANY && all)) {
       o.done = 1; o.done_mask |= 1 << ri; o.g_rew += ru.f[1];
     } else if (cond == MFG_DEST_SIMULTANEOUS) {
       wave_sync();
-      if (e.lane < n) e.dests()[e.lane] &= ~EW_REACHED;
+#pragma unroll
+      for (int h = 0; h < NW; h++)
+        if (h * MFG_WAVE + e.lane < n) e.dests()[h * MFG_WAVE + e.lane] &= ~EW_REACHED;
       wave_sync();
     }
   }
@@ -2170,19 +2200,19 @@ __device__ __attribute__((always_inline)) void env_reset(const Env& e, int* scra
         const int n = spawn_positions(e, q, ru.i[1], scratch);
         const int base = e.H(hc);
         e.setH(hb, base);
-        for (int i = 0; i < n; i++) spawn_into(e, tbl, hn, base, scratch[i]);
+        for (int i = 0; i < n; i++) spawn_into<NW>(e, tbl, hn, base, scratch[i]);
         e.setH(hc, base + n);
         wave_sync();
       }
     } else if (op == MFG_RULE_SPAWN_DIRT) {
       int v;
-      dirt_trigger_spawn(e, S->s.dirt_quantity, 0.0, &v, scratch);
+      dirt_trigger_spawn<NW>(e, S->s.dirt_quantity, 0.0, &v, scratch);
     } else if (op == MFG_RULE_SPAWN_GLOBALPOS) {
       e.setH(H_CNT_GP, e.H(H_CNT_GP) + A);
     } else if (op == MFG_RULE_SPAWN_DEST_ON_AGENT) {  // destinations/rules.py:155-162: bound, on the agent's cell
       const int base = e.H(H_CNT_DEST);
       e.setH(H_DEST_BASE, base);
-      for (int a = 0; a < A; a++) spawn_into(e, e.dests(), H_N_DESTS, base, uni(e.agpos()[a]), (a + 1) << EW_BOUND_SHIFT);
+      for (int a = 0; a < A; a++) spawn_into<NW>(e, e.dests(), H_N_DESTS, base, uni(e.agpos()[a]), (a + 1) << EW_BOUND_SHIFT);
       e.setH(H_CNT_DEST, base + A);
       wave_sync();
     } else if (op == MFG_RULE_SPAWN_DEST_PER_AGENT) {  // destinations/rules.py:116-133
@@ -2219,7 +2249,7 @@ __device__ __attribute__((always_inline)) void env_reset(const Env& e, int* scra
           if (c != apos && !grp_at(e.dests(), e.H(H_N_DESTS), c, EW_ALIVE, e.lane)) cell = c;
         }
         if (cell < 0) { reset_crash = MFG_CRASH_RULE; break; }  // exit(-9999) upstream
-        spawn_into(e, e.dests(), H_N_DESTS, base, cell, (a + 1) << EW_BOUND_SHIFT);
+        spawn_into<NW>(e, e.dests(), H_N_DESTS, base, cell, (a + 1) << EW_BOUND_SHIFT);
         made++;
       }
       e.setH(H_CNT_DEST, base + made);
@@ -2231,7 +2261,7 @@ __device__ __attribute__((always_inline)) void env_reset(const Env& e, int* scra
       const int hn = mach ? H_N_MACHINES : H_N_MAINTS, hc = mach ? H_CNT_MACHINE : H_CNT_MAINT;
       const int base = e.H(hc);
       e.setH(mach ? H_MACHINE_BASE : H_MAINT_BASE, base);
-      for (int i = 0; i < n; i++) spawn_into(e, mach ? e.machines() : e.maints(), hn, base, scratch[i]);
+      for (int i = 0; i < n; i++) spawn_into<NW>(e, mach ? e.machines() : e.maints(), hn, base, scratch[i]);
       e.setH(hc, base + n);
       wave_sync();
     }
@@ -2525,6 +2555,23 @@ struct SupT {  // per-agent suppression sets from the identifier dedupe
     return ((dsup[i >> 5] >> (i & 31)) & 1u) != 0;
   }
 };
+// Slots 64..127 of items, pods, drop-offs and destinations: a second word per group. Specs with such a group always
+// take the long-ray render (mfg_create), the one render compiled with it; the others keep one word per group.
+struct SupHi {
+  u64 items, pods, drops, dests;
+};
+template <typename DP>
+__device__ __forceinline__ void sup_add(SupT<DP>& s, int code, int xy, int lane);
+template <typename DP>
+__device__ __forceinline__ void sup_add_wide(SupT<DP>& s, SupHi& h, int code, int xy, int lane) {
+  const int kind = code >> 12, slot = code & 0xFFF;
+  if (slot < MFG_WAVE || kind < K_ITEM || kind == K_DIRT || kind > K_DEST) { sup_add(s, code, xy, lane); return; }
+  const u64 bit = 1ull << (slot & 63);
+  if (kind == K_ITEM) h.items |= bit;
+  else if (kind == K_POD) h.pods |= bit;
+  else if (kind == K_DROP) h.drops |= bit;
+  else h.dests |= bit;
+}
 template <typename DP>
 __device__ __forceinline__ void sup_add(SupT<DP>& s, int code, int xy, int lane) {
   const int kind = code >> 12, slot = code & 0xFFF;
@@ -2837,6 +2884,7 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
     // ---- identifier dedupe: of two visible entities with equal identifiers the later first visit loses
     SupT<tu32> sup;
     sup.items = sup.pods = sup.drops = sup.dests = sup.machines = sup.maints = 0;
+    SupHi suph{0, 0, 0, 0};  // (the long-ray render only)
     sup.wx0 = wx0; sup.wy0 = wy0; sup.oh = oh; sup.ow = ow; sup.W = W;
     sup.wsup = wsup;
     sup.dsup = dsup;
@@ -2857,8 +2905,13 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
         hm &= hm - 1;
         const int qq = q0 + L;
         const int codes = pairs.get(qq, 2);  // codeA | codeB << 16
-        if (rl((int)rA, L) < rl((int)rB, L)) sup_add(sup, (codes >> 16) & 0xFFFF, rl(pB, L), lane);
-        else sup_add(sup, codes & 0xFFFF, rl(pA, L), lane);
+        if constexpr (LR) {
+          if (rl((int)rA, L) < rl((int)rB, L)) sup_add_wide(sup, suph, (codes >> 16) & 0xFFFF, rl(pB, L), lane);
+          else sup_add_wide(sup, suph, codes & 0xFFFF, rl(pA, L), lane);
+        } else {
+          if (rl((int)rA, L) < rl((int)rB, L)) sup_add(sup, (codes >> 16) & 0xFFFF, rl(pB, L), lane);
+          else sup_add(sup, codes & 0xFFFF, rl(pA, L), lane);
+        }
       }
     }
     tbl_sync<LR>();
@@ -2965,10 +3018,28 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
         }
         tags = any ? (tags | (1u << tag)) : (tags & ~(1u << tag));
       };
-      resup(e.items(), e.H(H_N_ITEMS), sup.items, MFG_TAG_ITEMS, false);
-      resup(e.pods(), e.H(H_N_PODS), sup.pods, MFG_TAG_PODS, false);
-      resup(e.drops(), e.H(H_N_DROPS), sup.drops, MFG_TAG_DROPOFFS, false);
-      resup(e.dests(), e.H(H_N_DESTS), sup.dests, MFG_TAG_DESTS, true);
+      // the same over two words (slots 64..127 in sm2): the long-ray render
+      auto resup_wide = [&](const int* tbl, int n, u64 sm, u64 sm2, int tag, bool dest) {
+        if (!(sm | sm2)) return;
+        bool any = false;
+        for (int i = 0; i < n; i++) {
+          const int w = uni(tbl[i]);
+          const bool supd = (((i < MFG_WAVE ? sm : sm2) >> (i & (MFG_WAVE - 1))) & 1) != 0;
+          any |= v && EW_POS(w) == cell && (w & EW_PRESENT) && !supd && !(dest && (w & EW_REACHED));
+        }
+        tags = any ? (tags | (1u << tag)) : (tags & ~(1u << tag));
+      };
+      if constexpr (LR) {
+        resup_wide(e.items(), e.H(H_N_ITEMS), sup.items, suph.items, MFG_TAG_ITEMS, false);
+        resup_wide(e.pods(), e.H(H_N_PODS), sup.pods, suph.pods, MFG_TAG_PODS, false);
+        resup_wide(e.drops(), e.H(H_N_DROPS), sup.drops, suph.drops, MFG_TAG_DROPOFFS, false);
+        resup_wide(e.dests(), e.H(H_N_DESTS), sup.dests, suph.dests, MFG_TAG_DESTS, true);
+      } else {
+        resup(e.items(), e.H(H_N_ITEMS), sup.items, MFG_TAG_ITEMS, false);
+        resup(e.pods(), e.H(H_N_PODS), sup.pods, MFG_TAG_PODS, false);
+        resup(e.drops(), e.H(H_N_DROPS), sup.drops, MFG_TAG_DROPOFFS, false);
+        resup(e.dests(), e.H(H_N_DESTS), sup.dests, MFG_TAG_DESTS, true);
+      }
       if (MM && S->mmax) resup(e.machines(), e.H(H_N_MACHINES), sup.machines, MFG_TAG_MACHINES, false);
       if (MM && S->kmax) resup(e.maints(), e.H(H_N_MAINTS), sup.maints, MFG_TAG_MAINTAINERS, false);
       double dirt_amt = 0.0;

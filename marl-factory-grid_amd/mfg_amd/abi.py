@@ -8,6 +8,7 @@ MAX_LAYERS = 64
 MAX_COMBINED = 144
 MAX_RULES = 32
 MAX_DOORS = 128
+MAX_GROUP = 128  # items, charge pods, drop-off locations, destinations per env (MFG_MAX_GROUP)
 MAX_POSITIONS = 64
 
 # action opcodes

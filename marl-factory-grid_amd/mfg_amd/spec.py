@@ -501,6 +501,9 @@ def compile_spec(config_path, custom_level_path: Optional[str] = None, custom_mo
                   abi.RULE_SPAWN_MACHINES, abi.RULE_SPAWN_MAINTAINERS):
             if not isinstance(q, int) or q <= 0:
                 raise UnsupportedSpec(f'{g}: coords_or_quantity must be a positive int (None crashes upstream)')
+            if op in (abi.RULE_SPAWN_PODS, abi.RULE_SPAWN_DROPOFFS, abi.RULE_SPAWN_ITEMS,
+                      abi.RULE_SPAWN_DESTS) and q > abi.MAX_GROUP:
+                raise UnsupportedSpec(f'{g}: quantity {q} > {abi.MAX_GROUP} slots per env (MFG_MAX_GROUP)')
             ri[0] = q
             ri[1] = int(bool(kw.get('ignore_blocking', False)))
         rules.append((op, ri, rf))
@@ -515,8 +518,8 @@ def compile_spec(config_path, custom_level_path: Optional[str] = None, custom_mo
         if g in group_names and cap_needed > size + 1:
             raise UnsupportedSpec(f'{g}: {cap_needed} agents exceed LevelParser.size+1={size + 1} (Q16)')
 
-    if len(dest_entries) > abi.MAX_AGENTS:
-        raise UnsupportedSpec('too many SpawnDestinationsPerAgent entries')
+    if len(dest_entries) > 64:  # (the engine tests a candidate cell against one 64-slot pass of destinations)
+        raise UnsupportedSpec('Destinations: more than 64 SpawnDestinationsPerAgent entries')
     rays = ray_table(d if pomdp_r else min(H, W))  # RayCaster(agent, min(obs_shape)) (Q13)
     ray_off = np.zeros(len(rays) + 1, np.int32)
     ray_off[1:] = np.cumsum([len(r) for r in rays])
