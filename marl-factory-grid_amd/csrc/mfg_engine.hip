@@ -57,6 +57,7 @@ static int fail(const std::string& m) {
   g_err = m;
   return -1;
 }
+int mfg_internal_fail(const char* msg) { return fail(msg); }  // the other host units' (mfg_info.hip) way to the message
 #define HIPCHK(x)                                                               \
   do {                                                                          \
     hipError_t _e = (x);                                                        \

@@ -73,6 +73,21 @@ def load_lib():
     L.mfg_profile_read.restype = C.c_int
     L.mfg_hbm_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.mfg_hbm_copy.restype = C.c_int
+    # include/mfg_info.h: the info program (ops, n_ops, key_off, n_keys, action_table, n_agents, n_actions, noop_cost,
+    # dest_max) leads mfg_info_create and mfg_info_eval_host
+    prog = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int]
+    L.mfg_info_create.argtypes = prog + [C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]
+    L.mfg_info_destroy.argtypes = [C.c_void_p]
+    L.mfg_info_config.argtypes = [C.c_void_p, C.c_void_p]
+    L.mfg_info_step.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int64] + [C.c_void_p] * 8
+    L.mfg_info_episodes.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
+    L.mfg_info_rows.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 3
+    L.mfg_info_drain.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
+                                 C.c_void_p]
+    L.mfg_info_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mfg_info_eval_host.argtypes = prog + [C.c_void_p] * 7
+    for f in ('create', 'destroy', 'config', 'step', 'episodes', 'rows', 'drain', 'reset', 'eval_host'):
+        getattr(L, 'mfg_info_' + f).restype = C.c_int
     L.mfg_abi_version.restype = C.c_int
     if L.mfg_abi_version() != abi.ABI_VERSION:
         raise RuntimeError('libmfg_hip.so ABI version mismatch')
@@ -198,6 +213,89 @@ class Engine:
     def import_state(self, t):
         assert t.dtype == self.torch.uint8 and t.numel() == self.B * self.layout['size']
         _check(self.L.mfg_import_state(self.h, _ptr(t.contiguous()), self._stream()), 'mfg_import_state')
+
+
+class InfoMonitor:
+    """The device episode monitor of one compiled info program (include/mfg_info.h): per-step info columns and
+    their per-episode fold for `n_envs` envs, from the buffers of an `Engine.step` call. No CPU fallback."""
+
+    def __init__(self, program, n_envs, device=0, ep_capacity=None):
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError('mfg_amd.InfoMonitor needs a GPU (HIP); no CPU fallback exists')
+        self.torch = torch
+        self.L = load_lib()
+        self.program = program
+        self.B = int(n_envs)
+        self.device = torch.device('cuda', device) if isinstance(device, int) else torch.device(device)
+        self.ep_capacity = int(ep_capacity) if ep_capacity is not None else max(4 * self.B, 1024)
+        h = C.c_void_p()
+        _check(self.L.mfg_info_create(*program.c_args(), self.device.index or 0, self.B, self.ep_capacity,
+                                      C.byref(h)), 'mfg_info_create')
+        self.h = h
+        cfg = np.zeros(4, np.int32)
+        _check(self.L.mfg_info_config(self.h, cfg.ctypes.data), 'mfg_info_config')
+        self.Kc, self.keys_per_lane, self.waves_per_block, self.lds_bytes = (int(x) for x in cfg)
+
+    def close(self):
+        if getattr(self, 'h', None) is not None and self.h.value:
+            self.L.mfg_info_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def step(self, K, ev_act, ev_watch, ev_misc, reward, done, actions=None, philox_seed=0, env_base=0, step_base=0,
+             vals=None, pres=None):
+        """Fold the K steps an `Engine.step` call with the same K / actions / Philox arguments wrote into these
+        buffers; vals f64 / pres u8 [K, B, Kc] receive the per-step columns when given. Stream-ordered, no sync."""
+        A = self.program.n_agents
+        for t, n, dt in ((ev_act, K * self.B * A, self.torch.uint8), (ev_watch, K * self.B * A, self.torch.uint8),
+                         (ev_misc, K * self.B * EV_MISC, self.torch.int32),
+                         (reward, K * self.B * A, self.torch.float64), (done, K * self.B, self.torch.uint8),
+                         (actions, K * self.B * A, self.torch.int32), (vals, K * self.B * self.Kc, self.torch.float64),
+                         (pres, K * self.B * self.Kc, self.torch.uint8)):
+            if t is None:
+                continue
+            if t.numel() != n or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f'buffer must be a contiguous {dt} tensor of {n} elements on {self.device}')
+        _check(self.L.mfg_info_step(self.h, int(K), _ptr(actions), int(philox_seed) & 0xFFFFFFFF,
+                                    int(env_base) & 0xFFFFFFFF, int(step_base), _ptr(ev_act), _ptr(ev_watch),
+                                    _ptr(ev_misc), _ptr(reward), _ptr(done), _ptr(vals), _ptr(pres), self._stream()),
+               'mfg_info_step')
+
+    def reset(self, mask=None):
+        """Clear the accumulators of the envs with mask[b] != 0 (u8 [B] on the device; None: all)."""
+        if mask is not None and (mask.numel() != self.B or mask.dtype != self.torch.uint8 or not mask.is_contiguous()):
+            raise ValueError('mask must be a contiguous uint8 tensor [B]')
+        _check(self.L.mfg_info_reset(self.h, _ptr(mask), self._stream()), 'mfg_info_reset')
+
+    def episodes(self):
+        """Episodes finished since the last drain, dropped ones included (one sync)."""
+        n = C.c_uint32()
+        _check(self.L.mfg_info_episodes(self.h, C.byref(n), self._stream()), 'mfg_info_episodes')
+        return int(n.value)
+
+    def drain(self):
+        """(header i32 [n, 8], sum f64 [n, Kc], count u32 [n, Kc], dropped) of the finished episodes as numpy arrays,
+        sorted by (env, ep_index); the counter restarts at 0 (one sync)."""
+        n = self.episodes()
+        keep = min(n, self.ep_capacity)
+        hdr = np.zeros((keep, 8), np.int32)
+        s = np.zeros((keep, self.Kc), np.float64)
+        c = np.zeros((keep, self.Kc), np.uint32)
+        got = C.c_uint32()
+        _check(self.L.mfg_info_drain(self.h, keep, hdr.ctypes.data, s.ctypes.data, c.ctypes.data, C.byref(got),
+                                     self._stream()), 'mfg_info_drain')
+        assert got.value == n, 'episodes finished between the count and the drain on one stream'
+        order = np.lexsort((hdr[:, 1], hdr[:, 0]))
+        return hdr[order], s[order], c[order], n - keep
 
 
 class PackedObs:

@@ -16,6 +16,9 @@
   NotImplementedError like the reference (recorder.py:189-190).
 * `BatchedEpisodeLog` -- the batched counterpart: per-episode returns/lengths of a `VectorFactory`,
   collected from its step infos without per-step host copies of the whole batch.
+* `BatchedEnvMonitor` -- `EnvMonitor` for a `BatchedFactory` / `VectorFactory`: every env's info dict evaluated
+  and folded per episode on the device by one kernel per step (include/mfg_info.h, engine.InfoMonitor);
+  `frame()` is the reference's monitor DataFrame with one row per finished episode of any env.
 """
 import json
 import pickle
@@ -207,6 +210,115 @@ def _deltas(t1, t2):
 
     walk(t1, t2, 'root')
     return out
+
+
+def episode_frame(program, hdr, sums, counts):
+    """Finished-episode rows of the info monitor (include/mfg_info.h: header i32 [n, 8], sum f64 [n, Kc], count
+    u32 [n, Kc]) as the reference's monitor DataFrame (EnvMonitor._read_done): per episode, every info key present at
+    least once is summed, or averaged over the steps where it was present if it ends in 'ount'; IGNORED_DF_COLUMNS
+    are dropped; a key absent in an episode is NaN. Adds 'env', 'episode' (that env's episode index) and 'length'."""
+    import pandas as pd
+    from .info_program import HDR_ENV, HDR_EP_INDEX, HDR_LENGTH, HDR_MAINT_BASE
+    rows = []
+    for i in range(len(hdr)):
+        row = {'env': int(hdr[i][HDR_ENV]), 'episode': int(hdr[i][HDR_EP_INDEX]), 'length': int(hdr[i][HDR_LENGTH])}
+        for k in counts[i].nonzero()[0]:
+            name = program.column_name(int(k), hdr[i][HDR_MAINT_BASE])
+            if name in IGNORED_DF_COLUMNS:
+                continue
+            v = float(sums[i][k])
+            row[name] = v / int(counts[i][k]) if name.endswith('ount') else v
+        rows.append(row)
+    if not rows:
+        return pd.DataFrame(columns=['env', 'episode', 'length'])
+    return pd.DataFrame(rows)
+
+
+class BatchedEnvMonitor(_Wrapper):
+    """`EnvMonitor` for the batched engine: wraps a `BatchedFactory` or a `VectorFactory`; every step's info columns
+    are evaluated and folded per episode on the device (engine.InfoMonitor, one kernel on the env's stream, no host
+    sync and no per-step device->host copy). Finished episodes wait in a device buffer of `ep_capacity` rows until
+    `drain()` / `frame()` fetch them; episodes finishing while it is full are counted in `dropped`."""
+
+    def __init__(self, env, filepath=None, ep_capacity=None):
+        super().__init__(env)
+        from .engine import InfoMonitor
+        from .info_program import compile_info_program
+        self._vector = hasattr(env, 'num_envs')  # a VectorFactory keeps its BatchedFactory in .env
+        self._bf = env.env if self._vector else env
+        bf = self._bf
+        torch = bf.torch
+        self._filepath = filepath
+        self.program = compile_info_program(bf.spec)
+        self.monitor = InfoMonitor(self.program, bf.B, device=bf.device, ep_capacity=ep_capacity)
+        Kc = self.monitor.Kc
+        self._vals = torch.zeros((1, bf.B, Kc), dtype=torch.float64, device=bf.device)
+        self._pres = torch.zeros((1, bf.B, Kc), dtype=torch.uint8, device=bf.device)
+        self._hdr, self._sum, self._cnt = [], [], []
+        self.dropped = 0
+
+    def step(self, actions):
+        bf = self._bf
+        out = self.env.step(actions)
+        a = actions.to(device=bf.device, dtype=bf.torch.int32).contiguous()
+        self.monitor.step(1, bf.ev_act, bf.ev_watch, bf.ev_misc, bf.reward, bf.done, actions=a, vals=self._vals,
+                          pres=self._pres)
+        return out
+
+    def reset(self, mask=None, **kw):
+        """Forwarded to the env (a VectorFactory takes the mask as options={'mask': ...}); the masked envs' episode
+        accumulators restart (all envs without a mask)."""
+        bf = self._bf
+        m = None if mask is None else mask.to(device=bf.device, dtype=bf.torch.uint8).contiguous()
+        if self._vector:
+            out = self.env.reset(options=None if m is None else {'mask': m}, **kw)
+        else:
+            out = self.env.reset(mask=m, **kw)
+        self.monitor.reset(m)
+        return out
+
+    def step_columns(self):
+        """The last step's (names, values f64 [B, Kc], present bool [B, Kc]) on the device, as
+        `BatchedFactory.info_columns` returns them (a crashed env's row is 0 / absent)."""
+        return self.program.columns, self._vals[0], self._pres[0].bool()
+
+    def drain(self):
+        """Fetch the finished episodes from the device (one sync): host tensors env / episode / length / crashed /
+        maint_base [n], sum f64 [n, Kc], count i64 [n, Kc], sorted by (env, episode), and `dropped`, the number of
+        episodes that found the device buffer full since the last drain. The rows also feed `frame()`."""
+        import numpy as np
+        from .info_program import HDR_ENV, HDR_EP_INDEX, HDR_LENGTH, HDR_CRASHED, HDR_MAINT_BASE
+        torch = self._bf.torch
+        hdr, s, c, dropped = self.monitor.drain()
+        self._hdr.append(hdr)
+        self._sum.append(s)
+        self._cnt.append(c)
+        self.dropped += dropped
+        col = lambda j: torch.from_numpy(np.ascontiguousarray(hdr[:, j]))
+        return {'env': col(HDR_ENV), 'episode': col(HDR_EP_INDEX), 'length': col(HDR_LENGTH),
+                'crashed': col(HDR_CRASHED), 'maint_base': col(HDR_MAINT_BASE), 'sum': torch.from_numpy(s),
+                'count': torch.from_numpy(c.astype(np.int64)), 'dropped': dropped}
+
+    def frame(self):
+        """One row per finished episode so far (drains first), in drain order: see `episode_frame`."""
+        import numpy as np
+        self.drain()
+        return episode_frame(self.program, np.concatenate(self._hdr), np.concatenate(self._sum),
+                             np.concatenate(self._cnt))
+
+    @property
+    def monitor_df(self):
+        return self.frame()
+
+    def save_monitor(self, filepath=None):
+        filepath = Path(filepath or self._filepath)
+        filepath.parent.mkdir(exist_ok=True, parents=True)
+        with filepath.open('wb') as f:
+            pickle.dump(self.frame().reset_index(), f, protocol=pickle.HIGHEST_PROTOCOL)
+
+    def close(self):
+        self.monitor.close()
+        self.env.close()
 
 
 class BatchedEpisodeLog:

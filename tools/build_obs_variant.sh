@@ -20,7 +20,7 @@ for p in "${pids[@]}"; do wait $p; done
 for arg in "$@"; do
   name=${arg%%=*}
   objs=""
-  for u in mfg_engine mfg_obs_a mfg_obs_b mfg_obs_c mfg_obs_d mfg_obs_e mfg_obs_f mfg_learn; do
+  for u in mfg_engine mfg_obs_a mfg_obs_b mfg_obs_c mfg_obs_d mfg_obs_e mfg_obs_f mfg_learn mfg_info; do
     if [[ " $VU " == *" $u "* ]]; then objs="$objs build/obj/${u}_$name.o"; else objs="$objs build/obj/$u.o"; fi
   done
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/ablate/libmfg_hip_$name.so $objs
