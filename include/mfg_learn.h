@@ -44,6 +44,34 @@ int mfg_packed_project(const uint16_t* idx, const float* val, int64_t m, int cap
 int mfg_sample_categorical(const float* logits, int64_t logit_row, int n_act, const float* u, int64_t n, int32_t* out,
                            void* stream);
 
+/* ---- the PPO loss head of the MAPPO learner (marl.py BatchedMAPPO; algorithms/marl/mappo.py:30-66), mfg_ppo.hip.
+ * Both calls reduce deterministically (per-block partials in `ws`, then a one-block finishing pass in a fixed order;
+ * no floating-point atomics): the same input gives bit-identical output on every run. `ws` is caller-provided
+ * device scratch of at least MFG_PPO_WS_BYTES bytes (8-byte aligned) for any size; one buffer can serve both calls
+ * on one stream. */
+#define MFG_PPO_WS_BYTES 16384
+
+/* ret[i][s] = reward[i][s] + gamma (1 - done[i][s]) ret[i][s+1], ret[i][t] = 0 (mappo.py:30-37), rows i < n, steps
+ * s < t, *_row = row strides in elements (>= t); stats[0] = the mean and stats[1] = the unbiased (n t - 1) standard
+ * deviation of all n t returns (mappo.py:48, torch.std), accumulated in f64, written as device doubles.
+ * -1 when n t < 2 (no unbiased deviation). */
+int mfg_mc_returns(const float* reward, int64_t rew_row, const float* done, int64_t done_row, int64_t n, int t,
+                   float gamma, float* ret, int64_t ret_row, double* stats, void* ws, void* stream);
+
+/* Forward and backward of mappo.py:41-66 over m = n t elements: logits / old_logits [m][n_act] (row strides
+ * logit_row / old_row), critic, ret f32 [m], action i32 [m], stats from mfg_mc_returns. With
+ * R = (ret - stats[0]) / (stats[1] + 1e-8), adv = R - critic, ratio = exp(logp[a] - old_logp[a]):
+ *   loss[0] = mean_i( -min(ratio adv, clamp(ratio, 1 - c, 1 + c) adv) + vf adv^2 - ent H(softmax(logits_i)) )
+ * and, for a loss gradient of 1, dlogits [m][n_act] (row stride dlogit_row) and dcritic [m]. adv is a constant in
+ * the surrogate and differentiated in the value term; where the surrogates tie the gradient follows torch.min (an
+ * even split) and torch.clamp (gradient at and inside the bounds), so inside the clip range it is adv through ratio.
+ * An action outside [0, n_act) or non-finite logits in an element: loss[0] = NaN, that element's gradients 0, and
+ * nothing is read or written out of bounds. */
+int mfg_ppo_head(const float* logits, int64_t logit_row, const float* old_logits, int64_t old_row,
+                 const float* critic, const int32_t* action, const float* ret, const double* stats, int64_t m,
+                 int n_act, float clip_range, float vf_coef, float entropy_coef, float* loss, float* dlogits,
+                 int64_t dlogit_row, float* dcritic, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

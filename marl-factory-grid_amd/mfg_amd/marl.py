@@ -987,3 +987,385 @@ class BatchedA2C:
         for _ in range(n_updates * self.T):
             self.step()
         return self.last_loss
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# MAPPO: the reference's PPO learner on the same shared RecurrentAC (algorithms/marl/mappo.py LoopMAPPO)
+# ---------------------------------------------------------------------------------------------------------------------
+_PPO_LIB = None
+_PPO_WS_BYTES = 16384  # MFG_PPO_WS_BYTES (include/mfg_learn.h)
+
+
+def _ppo_lib():
+    """libmfg_hip.so's PPO loss head (include/mfg_learn.h, csrc/mfg_ppo.hip), bound once."""
+    global _PPO_LIB
+    if _PPO_LIB is None:
+        import ctypes as C
+        L = _gru_lib()
+        p, i64, f32 = C.c_void_p, C.c_int64, C.c_float
+        L.mfg_mc_returns.argtypes = [p, i64, p, i64, i64, C.c_int, f32, p, i64, p, p, p]
+        L.mfg_mc_returns.restype = C.c_int
+        L.mfg_ppo_head.argtypes = [p, i64, p, i64, p, p, p, p, i64, C.c_int, f32, f32, f32, p, p, i64, p, p, p]
+        L.mfg_ppo_head.restype = C.c_int
+        _PPO_LIB = L
+    return _PPO_LIB
+
+
+def monte_carlo_returns(reward, done, gamma):
+    """mappo.py:30-37: R_t = r_t + gamma (1 - d_t) R_{t+1} per row of reward / done [N, T], R_T = 0."""
+    acc = torch.zeros_like(reward[:, -1])
+    outs = []
+    for t in range(reward.shape[1] - 1, -1, -1):
+        acc = reward[:, t] + (gamma * (1.0 - done[:, t]) * acc)
+        outs.insert(0, acc)
+    return torch.stack(outs, dim=1)
+
+
+def mappo_loss(out, old_logits, actions, reward, done, gamma, entropy_coef, vf_coef, clip_range):
+    """mappo.py:41-66 on a forward output of T+1 entries, with a2c_loss's shapes: actions [N, T+1] (entry 0 = the
+    action before the window), old_logits [N, T, n_act] (the acting logits of entries 0..T-1), reward / done [N, T].
+    Entry T of the forward is dead here (Monte-Carlo returns need no bootstrap value)."""
+    return mappo_loss_terms(out['logits'][:, :-1], out['critic'][:, :-1], old_logits, actions[:, 1:], reward, done,
+                            gamma, entropy_coef, vf_coef, clip_range)
+
+
+def mappo_loss_terms(logits, critic, old_logits, actions, reward, done, gamma, entropy_coef, vf_coef, clip_range):
+    """mappo_loss on the logits [N, T, n_act] and critic [N, T] of entries 0..T-1 and their actions [N, T]."""
+    index = actions.unsqueeze(-1)
+    old_log_probs = torch.gather(torch.log_softmax(old_logits, -1), dim=-1, index=index).squeeze(-1)
+    mc_returns = monte_carlo_returns(reward, done, gamma)
+    mc_returns = (mc_returns - mc_returns.mean()) / (mc_returns.std() + 1e-8)
+    advantages = mc_returns - critic
+    log_ap = torch.gather(torch.log_softmax(logits, -1), dim=-1, index=index).squeeze(-1)
+    ratio = (log_ap - old_log_probs).exp()
+    surr1 = ratio * advantages.detach()
+    surr2 = torch.clamp(ratio, 1 - clip_range, 1 + clip_range) * advantages.detach()
+    policy_loss = -torch.min(surr1, surr2).mean(-1)
+    entropy_loss = Categorical(logits=logits, validate_args=False).entropy().mean(-1)
+    value_loss = advantages.pow(2).mean(-1)
+    loss = policy_loss + vf_coef * value_loss - entropy_coef * entropy_loss
+    return loss.mean()
+
+
+class _PPOHead(torch.autograd.Function):
+    """mappo_loss_terms on the GPU as two HIP calls: mfg_mc_returns (returns, their mean and unbiased std) and
+    mfg_ppo_head (loss, dlogits and dcritic in one pass; include/mfg_learn.h). The forward keeps both gradients for
+    a loss gradient of 1; the backward scales them. A NaN loss marks an action outside [0, n_act) or non-finite
+    logits (BatchedMAPPO raises on it when check_cap is set)."""
+
+    @staticmethod
+    def forward(ctx, logits, critic, old_logits, actions, reward, done, gamma, entropy_coef, vf_coef, clip_range):
+        n, t, n_act = logits.shape
+        dev = logits.device
+        L, st = _ppo_lib(), torch.cuda.current_stream(dev).cuda_stream
+        lg = logits.detach().reshape(n * t, n_act).float().contiguous()
+        old = old_logits.reshape(n * t, n_act).float().contiguous()
+        cr = critic.detach().reshape(n * t).float().contiguous()
+        act = actions.reshape(n * t).to(torch.int32).contiguous()
+        rew, dn = reward.float().contiguous(), done.float().contiguous()
+        ret = torch.empty((n, t), dtype=torch.float32, device=dev)
+        stats = torch.empty(2, dtype=torch.float64, device=dev)
+        ws = torch.empty(_PPO_WS_BYTES // 8, dtype=torch.float64, device=dev)
+        if L.mfg_mc_returns(rew.data_ptr(), t, dn.data_ptr(), t, n, t, gamma, ret.data_ptr(), t, stats.data_ptr(),
+                            ws.data_ptr(), st):
+            raise RuntimeError('mfg_mc_returns failed (a minibatch needs at least two elements)')
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        dlogits = torch.empty((n * t, n_act), dtype=torch.float32, device=dev)
+        dcritic = torch.empty(n * t, dtype=torch.float32, device=dev)
+        if L.mfg_ppo_head(lg.data_ptr(), n_act, old.data_ptr(), n_act, cr.data_ptr(), act.data_ptr(), ret.data_ptr(),
+                          stats.data_ptr(), n * t, n_act, clip_range, vf_coef, entropy_coef, loss.data_ptr(),
+                          dlogits.data_ptr(), n_act, dcritic.data_ptr(), ws.data_ptr(), st):
+            raise RuntimeError('mfg_ppo_head failed')
+        ctx.save_for_backward(dlogits.view(n, t, n_act), dcritic.view(n, t))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dlogits, dcritic = ctx.saved_tensors
+        return (g * dlogits, g * dcritic) + (None,) * 8
+
+
+def _window_any(flags, chunk_len, lo_off, hi_off):
+    """any(flags[:, s + lo_off : s + hi_off]) for the starts s < S - chunk_len, windows clipped to [0, S)."""
+    n, s_len = flags.shape
+    c = torch.zeros((n, s_len + 1), dtype=torch.long, device=flags.device)
+    c[:, 1:] = (flags != 0).long().cumsum(1)
+    s = torch.arange(s_len - chunk_len, device=flags.device)
+    lo, hi = (s + lo_off).clamp(0, s_len), (s + hi_off).clamp(0, s_len)
+    return (c[:, hi] - c[:, lo]) > 0
+
+
+def chunk_starts(done, chunk_len, rule='episode'):
+    """The valid chunk starts [N, S - chunk_len] (bool) of per-row done flags [N, S]: a chunk at start s covers the
+    entries s .. s + chunk_len - 1 of its row.
+
+    rule='reference' reproduces ``ExperienceChunks.whitelist`` (memory.py:146-151) exactly: every done index d
+    excludes the starts max(0, d - chunk_len - 1) .. d + 1, and start 0 is always excluded. A chunk therefore never
+    contains a terminal step (nor the two entries before one), so the reward of an episode's last step is never
+    trained on, and neither is the oldest entry of the buffer.
+    rule='episode' (the default) excludes a start only when the chunk would cross an episode end: all its entries lie
+    in one episode, i.e. a done flag is allowed on the chunk's last entry only. Terminal rewards reach the learner,
+    and the Monte-Carlo return of such a chunk ends where the episode does."""
+    if rule == 'reference':
+        bad = _window_any(done, chunk_len, -1, chunk_len + 2)
+        bad[:, :1] = True
+    elif rule == 'episode':
+        bad = _window_any(done, chunk_len, 0, chunk_len - 1)
+    else:
+        raise ValueError("chunk rule must be 'episode' or 'reference'")
+    return ~bad
+
+
+def _draw_uniform(mask, u):
+    """A uniform draw among the True entries of mask (at least one per row) at the uniforms u [M] in [0, 1): the
+    index of the floor(u * count)-th True entry, per row of mask [M, K], or M draws from one row mask [K]."""
+    c = mask.long().cumsum(-1)
+    tot = c[..., -1:]
+    k = torch.minimum((u[:, None].double() * tot).long(), tot - 1) + 1  # [M, 1]: the rank of the picked entry
+    if mask.dim() == 1:
+        return torch.searchsorted(c, k.squeeze(1))
+    return torch.searchsorted(c, k).squeeze(1)
+
+
+class BatchedMAPPO:
+    """MAPPO (``algorithms/marl/mappo.py`` ``LoopMAPPO``) with a shared ``RecurrentAC`` over B envs x A agents of one
+    engine, everything on the device: a clipped PPO surrogate on normalised Monte-Carlo returns, a replay buffer of
+    ``buffer_size`` steps, ``n_updates`` minibatches of ``batch_size`` chunks of ``n_steps`` steps per learn call,
+    Adam(lr 3e-4, eps 1e-5) and ``clip_grad_norm_(0.5)`` (``mappo.py:14-28``).
+
+    Acting is ``BatchedA2C``'s (without the stored-activation reuse): the engine renders o_t as packed rows + the
+    fused ``obs_proj``, the policy acts on (o_t, a_{t-1}, h_t) through ``forward_emb``, ``_sample`` draws the action,
+    the engine steps with ``auto_reset``; after a done the next entry's action input is -1 and its recurrent state
+    zero. The memory is aligned as in ``BatchedA2C``: entry t holds (o_t, a_{t-1}) as the network input and a_t, r_t,
+    d_t as targets.
+
+    The buffer is a ring of ``buffer_size + 1`` slots on the device: ``buffer_size`` complete entries (a FIFO, as
+    the reference's memory with ``reset_memory_after_epoch = False``) and the pending one at the write head, whose
+    observation is rendered but whose action, reward and done are not known yet. Per slot: the packed observation
+    (one ``PackedObs`` slot), the action input, the action, reward, done, the acting logits and both recurrent
+    states fed at that entry (the largest part: 2 S N H 4 bytes). Chunks are addressed in FIFO order (oldest = 0),
+    so a chunk never spans the write head, whatever the ring position.
+
+    Learning: once the buffer is full, every ``n_steps`` steps, ``n_updates`` minibatches. A minibatch draws
+    ``batch_size`` (row, start) pairs: the row uniformly among the N = B x A rows that have a valid start
+    (``chunk_starts``, ``chunk_rule``), the start uniformly among that row's valid starts. The reference draws
+    ``batch_size`` chunks per agent memory (one env); here it is ``batch_size`` chunks per minibatch over all rows.
+    ``obs_proj`` is re-evaluated on the stored entries with the current weights (``project_packed``: the projection
+    fused at render time is stale after the first minibatch), then ``forward_emb`` from the chunk's stored recurrent
+    states without restarts (entries 0..T-1 only: entry T is dead in this loss), the loss head (``_PPOHead``: one HIP
+    pass for loss and gradients on the GPU with ``fused_head``; ``mappo_loss_terms`` otherwise and on the CPU),
+    gradient clipping and Adam. After a learn call the engine's projection weights are refreshed and the pending
+    observation re-projected, as ``BatchedA2C._update`` does.
+
+    ``episodes`` / ``reward_sum`` fold in the last ``n_steps`` entries at every learn call, ``updates`` counts
+    minibatch updates, ``skipped_updates`` the minibatches skipped because no row had a valid start. With
+    ``check_cap`` a learn call raises on truncated packed rows, on non-finite acting logits and on a non-finite
+    loss (one host sync each)."""
+
+    _sample = BatchedA2C._sample
+
+    def __init__(self, factory, net=None, n_steps=5, buffer_size=20, batch_size=1024, n_updates=4, gamma=0.99,
+                 entropy_coef=0.01, vf_coef=0.5, clip_range=0.2, lr=3e-4, cap=32, obs_emb_size=96, action_emb_size=16,
+                 hidden_size=64, use_agent_embedding=False, chunk_rule='episode', fused_head=True, check_cap=True,
+                 generator=None):
+        from .engine import PackedObs
+        self.f = factory
+        eng = factory.engine
+        self.B, self.A = eng.B, eng.A
+        self.N = self.B * self.A
+        self.dev = eng.device
+        n_act = set(int(x) for x in factory.spec.n_actions)
+        if len(n_act) != 1:
+            raise ValueError('BatchedMAPPO shares one network: all agents need the same number of actions')
+        self.n_actions = n_act.pop()
+        if buffer_size < n_steps + 1:
+            raise ValueError(f'buffer_size {buffer_size} holds no chunk start: it must be at least n_steps + 1 = '
+                             f'{n_steps + 1}')
+        if chunk_rule not in ('episode', 'reference'):
+            raise ValueError("chunk_rule must be 'episode' or 'reference'")
+        kdim = eng.lmax * eng.obs_hw[0] * eng.obs_hw[1]
+        if not check_cap and cap < kdim:
+            raise ValueError(f'check_cap=False needs cap >= lmax*h*w = {kdim} (rows can hold up to that many '
+                             f'nonzero entries); got cap {cap}')
+        self.net = net if net is not None else RecurrentAC(
+            kdim, self.n_actions, obs_emb_size, action_emb_size, hidden_size, hidden_size, self.A,
+            use_agent_embedding=use_agent_embedding)
+        self.net.to(self.dev)
+        self.opt = torch.optim.Adam(self.net.parameters(), lr=lr, eps=1e-5)  # mappo.py:16
+        self.T, self.S, self.batch_size, self.n_updates = n_steps, buffer_size, batch_size, n_updates
+        self.gamma, self.entropy_coef, self.vf_coef, self.clip_range = gamma, entropy_coef, vf_coef, clip_range
+        self.chunk_rule, self.check_cap, self.gen = chunk_rule, check_cap, generator
+        self.fused_head = bool(fused_head)
+        R, N, dev = buffer_size + 1, self.N, self.dev
+        self.R = R
+        self.pobs = PackedObs(eng, K=R, cap=cap, weight=self.net.obs_proj.weight, bias=self.net.obs_proj.bias)
+        self.slot = [self.pobs.view(k) for k in range(R)]
+        self.act_in = torch.full((R, self.B, self.A), -1, dtype=torch.int64, device=dev)  # a_{t-1}, -1 = none
+        self.act = torch.zeros((R, self.B, self.A), dtype=torch.int32, device=dev)
+        self.rew = torch.zeros((R, self.B, self.A), dtype=torch.float64, device=dev)
+        self.done = torch.zeros((R, self.B), dtype=torch.uint8, device=dev)
+        self.logits = torch.zeros((R, N, self.n_actions), device=dev)  # the acting logits (the loss's old policy)
+        self.ha_in = torch.zeros((R, N, self.net.hidden_size_actor), device=dev)  # recurrent states fed at the entry
+        self.hc_in = torch.zeros((R, N, self.net.hidden_size_critic), device=dev)
+        self.ha = torch.zeros((N, 1, self.net.hidden_size_actor), device=dev)
+        self.hc = torch.zeros((N, 1, self.net.hidden_size_critic), device=dev)
+        self._u = torch.empty(N, device=dev)
+        self.agent_ids = torch.arange(self.A, device=dev).repeat(self.B)
+        self.last_loss = torch.zeros((), device=dev)
+        self.head = 0  # the ring slot of the pending entry
+        self.filled = 0  # complete entries, at most S
+        self.steps = 0
+        self.updates = 0
+        self.skipped_updates = 0
+        self.episodes = torch.zeros((), dtype=torch.float64, device=dev)
+        self.reward_sum = torch.zeros((), dtype=torch.float64, device=dev)
+        self._started = False
+
+    def buffer_bytes(self):
+        """Device bytes of the ring (all R = buffer_size + 1 slots)."""
+        bufs = [self.pobs.idx, self.pobs.val, self.pobs.count, self.pobs.emb, self.act_in, self.act, self.rew,
+                self.done, self.logits, self.ha_in, self.hc_in]
+        return sum(b.numel() * b.element_size() for b in bufs)
+
+    def reset(self):
+        self.f.engine.reset(obs=self.slot[self.head], init=0 if self.f._created else 1, seed_base=self.f.seed_base)
+        self.f._created = True
+        self._started = True
+        self.act_in[self.head].fill_(-1)
+        self.ha.zero_()
+        self.hc.zero_()
+        self.filled = 0  # the stored entries belong to other episodes
+
+    @torch.no_grad()
+    def step(self):
+        """One env-step of every env with the current policy; a learn call every n_steps steps."""
+        if not self._started:
+            self.reset()
+        h = self.head
+        nxt = (h + 1) % self.R
+        self.ha_in[h].copy_(self.ha[:, 0])
+        self.hc_in[h].copy_(self.hc[:, 0])
+        out = self.net.forward_emb(self.pobs.emb[h].view(self.N, 1, -1), self.act_in[h].view(self.N, 1), self.ha,
+                                   self.hc, agent_ids=self.agent_ids)
+        self.logits[h].copy_(out['logits'][:, 0])
+        self._sample(self.logits[h], h)
+        self.f.engine.step(1, actions=self.act[h], reward=self.rew[h], done=self.done[h], obs=self.slot[nxt],
+                           auto_reset=True, step_base=self.f.t)
+        self.f.t += 1
+        d = self.done[h].bool()
+        a = self.act[h].long()
+        self.act_in[nxt].copy_(torch.where(d.view(-1, 1), torch.full_like(a, -1), a))
+        keep = (~d).to(self.ha.dtype).view(self.B, 1, 1)  # broadcast over the env's agents
+        torch.mul(out['hidden_actor'].view(self.B, self.A, -1), keep, out=self.ha.view(self.B, self.A, -1))
+        torch.mul(out['hidden_critic'].view(self.B, self.A, -1), keep, out=self.hc.view(self.B, self.A, -1))
+        self.head = nxt
+        self.filled = min(self.filled + 1, self.S)
+        self.steps += 1
+        if self.steps % self.T == 0:
+            self.learn()
+
+    def order(self):
+        """The ring slots of the complete entries in FIFO order, oldest first [filled]."""
+        k = torch.arange(self.filled, device=self.dev)
+        return (self.head - self.filled + k) % self.R
+
+    def sample(self):
+        """(rows [batch_size], starts [batch_size]) of one minibatch: rows of the [N] agent rows, starts in FIFO
+        coordinates of the full buffer; None when no row has a valid start."""
+        if self.filled < self.S:
+            raise RuntimeError('BatchedMAPPO.sample: the buffer is not full yet')
+        d = self.done[self.order()].t().repeat_interleave(self.A, 0)  # [N, S]
+        mask = chunk_starts(d, self.T, self.chunk_rule)
+        row_ok = mask.any(1)
+        if not bool(row_ok.any()):
+            return None
+        u = torch.rand((2, self.batch_size), device=self.dev, generator=self.gen)
+        rows = _draw_uniform(row_ok, u[0])
+        starts = _draw_uniform(mask[rows], u[1])
+        return rows, starts
+
+    def minibatch(self, rows, starts):
+        """The chunks (row, start) gathered from the ring: packed rows, inputs, stored states and targets."""
+        T, R, N = self.T, self.R, self.N
+        slots = self.order()[starts[:, None] + torch.arange(T, device=self.dev)]  # [Bm, T] ring slots
+        r2 = rows[:, None]
+        pb = self.pobs
+        cap = pb.cap
+        idx = pb.idx.view(torch.int16).view(R, N, cap)[slots, r2].view(torch.uint16)  # (no uint16 gather: a bit view)
+        val = pb.val.view(R, N, cap)[slots, r2]
+        return dict(rows=rows, starts=starts, slots=slots, idx=idx, val=val,
+                    act_in=self.act_in.view(R, N)[slots, r2], act=self.act.view(R, N)[slots, r2].long(),
+                    reward=self.rew.view(R, N)[slots, r2].to(torch.float32),
+                    done=self.done[slots, r2 // self.A].to(torch.float32), old_logits=self.logits[slots, r2],
+                    ha=self.ha_in[slots[:, 0], rows][:, None], hc=self.hc_in[slots[:, 0], rows][:, None],
+                    agent_ids=self.agent_ids[rows])
+
+    def evaluate(self, mb):
+        """The chunk forward with the current weights: obs_proj on the stored entries, then forward_emb from the
+        stored recurrent states (no restarts: a valid chunk holds no episode start after its first entry)."""
+        emb = self.net.project_packed(mb['idx'], mb['val'])
+        return self.net.forward_emb(emb, mb['act_in'], mb['ha'], mb['hc'], agent_ids=mb['agent_ids'])
+
+    def loss(self, mb, out=None):
+        """The MAPPO loss of a minibatch (mappo.py:39-66), with grad."""
+        with torch.enable_grad():
+            out = self.evaluate(mb) if out is None else out
+            args = (out['logits'], out['critic'], mb['old_logits'], mb['act'], mb['reward'], mb['done'], self.gamma,
+                    self.entropy_coef, self.vf_coef, self.clip_range)
+            if self.fused_head and out['logits'].is_cuda:
+                return _PPOHead.apply(*args)
+            return mappo_loss_terms(*args)
+
+    def learn(self):
+        """n_updates minibatch updates once the buffer is full (mappo.py:18-28), then the engine's projection
+        weights are refreshed."""
+        last = (self.head - 1 - torch.arange(min(self.T, self.filled), device=self.dev)) % self.R
+        self.episodes += self.done[last].sum()
+        self.reward_sum += self.rew[last].sum()
+        if self.filled < self.S:
+            return
+        if self.check_cap:
+            self.pobs.check()
+            if self.gen is None and self.dev.type == 'cuda' and bool((self.act < 0).any()):
+                raise RuntimeError('BatchedMAPPO: non-finite policy logits while acting (training diverged)')
+        for _ in range(self.n_updates):
+            picked = self.sample()
+            if picked is None:
+                self.skipped_updates += 1
+                continue
+            self._update(self.minibatch(*picked))
+        with torch.no_grad():
+            # new weights: the engine projects with them from now on; the pending observation's projection is redone
+            self.pobs.set_projection(self.net.obs_proj.weight, self.net.obs_proj.bias)
+            self._project_slot(self.head)
+        if self.check_cap and not bool(torch.isfinite(self.last_loss)):
+            raise RuntimeError('BatchedMAPPO: non-finite loss (an action outside the action range or non-finite '
+                               'logits in a minibatch)')
+
+    def _update(self, mb):
+        with torch.enable_grad():
+            loss = self.loss(mb)
+            self.opt.zero_grad(set_to_none=True)
+            loss.backward()
+            torch.nn.utils.clip_grad_norm_(self.net.parameters(), 0.5)
+            self.opt.step()
+        self.last_loss.copy_(loss.detach())
+        self.updates += 1
+
+    def _project_slot(self, k):
+        """Slot k's fused projection redone with the current weights (BatchedA2C._project_slot0)."""
+        pb = self.pobs
+        if not pb.idx.is_cuda:
+            pb.emb[k].copy_(_project_dense(pb.idx[k], pb.val[k], self.net.obs_proj))
+            return
+        rc = _gru_lib().mfg_packed_project(pb.idx[k].data_ptr(), pb.val[k].data_ptr(), self.N, pb.cap, pb.wt.data_ptr(),
+                                           pb.bias.data_ptr(), pb.E, pb.kdim, pb.emb[k].data_ptr(), pb.E,
+                                           torch.cuda.current_stream(self.dev).cuda_stream)
+        if rc:
+            raise RuntimeError('mfg_packed_project failed')
+
+    def train(self, n_steps):
+        """n_steps env-steps (with the learn calls that fall into them); returns the last minibatch loss."""
+        for _ in range(n_steps):
+            self.step()
+        return self.last_loss
