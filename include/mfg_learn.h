@@ -72,6 +72,56 @@ int mfg_ppo_head(const float* logits, int64_t logit_row, const float* old_logits
                  int n_act, float clip_range, float vf_coef, float entropy_coef, float* loss, float* dlogits,
                  int64_t dlogit_row, float* dcritic, void* ws, void* stream);
 
+/* ---- per-agent networks (marl.py AgentNets, BatchedIAC / BatchedSEAC; algorithms/marl/iac.py, seac.py),
+ * mfg_seac.hip. G networks with their parameters stacked on a leading axis. */
+
+/* obs_proj of packed rows by per-agent weights: idx u16 / val f32 [m][cap] in engine order (row r belongs to agent
+ * r % g, m % g == 0), wt [g][k][e_dim] (= obs_proj.weight^T per network), bias [g][e_dim]. Written agent-major with
+ * mb = m / g rows per agent (row stride out_row >= e_dim, columns past e_dim untouched):
+ *   all == 0:  out[r % g][r / g]       = bias[r % g] + sum_j val[r][j] wt[r % g][idx[r][j]]
+ *   all != 0:  out[n][r % g][r / g]    = bias[n] + sum_j val[r][j] wt[n][idx[r][j]]  for every network n < g
+ * (the row's entries are read once for all g projections). Every one of the cap entries is visited; zero values and
+ * indices >= k are skipped. -1 for m % g != 0, k > 4096, e_dim > 128 or cap > 2048. */
+int mfg_packed_project_grouped(const uint16_t* idx, const float* val, int64_t m, int cap, int g, const float* wt,
+                               const float* bias, int e_dim, int k, int all, float* out, int64_t out_row,
+                               void* stream);
+
+/* mfg_gru_fwd_step with one recurrent bias per block of rows: row r uses bh[r / rows_per_group][3 hd]
+ * (n % rows_per_group == 0). The same arithmetic otherwise. (mfg_gru_bwd_step reads no bias: it serves grouped rows
+ * unchanged.) */
+int mfg_gru_fwd_step_grouped(const float* gi, int64_t gi_row, const float* gh0, const float* bh,
+                             int64_t rows_per_group, const float* h, int64_t h_row, const float* keep,
+                             int64_t keep_row, float* h_out, int64_t ho_row, float* hp_out, float* r_out,
+                             float* z_out, float* n_out, float* ghn_out, int64_t sv_row, int64_t n, int hd,
+                             void* stream);
+
+/* Device scratch of mfg_seac_head for g networks (8-byte aligned), whatever the number of rows. */
+#define MFG_SEAC_WS_BYTES(g) ((g) * 4096)
+
+/* The IAC / SEAC loss of all A = n_agents networks with its gradients, for a loss gradient of 1 per network. Rows are
+ * agent-major: row = agent * n_envs + env, n = n_agents * n_envs; entries 0..t of a row (t targets, t <= 255).
+ *   cross != 0 (SEAC, seac.py:12-47):  logits [A][n][t+1][n_max], critic [A][n][t+1]: every network on every row;
+ *   cross == 0 (IAC, base_ac.py:200-217 per agent):  logits [n][t+1][n_max], critic [n][t+1]: a row by its own network;
+ * dlogits / dcritic have the shapes of logits / critic, loss is [A]. action i32, reward f32, done f32 of step s < t,
+ * env b, agent i are read at s * x_step + b * x_env + i * x_agent (elements), so [T][B][A] engine buffers are read in
+ * place. n_act [A] (device): network j's head uses its first n_act[j] <= n_max logits.
+ *   td_s = reward_s + gamma (1 - done_s) critic[s+1] - critic[s]   (critic[s+1] a constant)
+ *   adv_s = td_s (gae_coef <= 0), else adv_s = td_s + gamma gae_coef (1 - done_s) adv_{s+1}
+ *   logp = log_softmax(logits[j][row][s])[action];  iw = exp(logp_j - logp_{agent(row)}) (a constant; 1 for cross == 0)
+ *   cross:  loss[j] = mean_{row,s}(-iw logp adv + vf iw adv^2) - ent mean_{row of agent j, s} H(softmax(logits))
+ *   own:    loss[j] = mean_{row of agent j, s}(-logp adv + vf adv^2 - ent H)
+ * adv is a constant in the policy term and differentiated in the value term through critic[s] only. dcritic of entry
+ * t, dlogits of entry t and of columns >= n_act[j] are 0. An action outside [0, n_act[j]), a non-finite logit (of
+ * network j or, for iw, of the row's own network) or n_act[j] outside [1, n_max]: that element's gradients are 0
+ * and every loss it enters is NaN; nothing is read or written out of bounds. Deterministic: per-block f64 partials
+ * in `ws` (>= MFG_SEAC_WS_BYTES(n_agents) bytes), added in a fixed order; no floating-point atomics. */
+int mfg_seac_head(const float* logits, const float* critic, int n_agents, int64_t n_envs, int t, int n_max,
+                  const int32_t* action, int64_t act_step, int64_t act_env, int64_t act_agent,
+                  const float* reward, int64_t rew_step, int64_t rew_env, int64_t rew_agent,
+                  const float* done, int64_t done_step, int64_t done_env, int64_t done_agent,
+                  const int32_t* n_act, float gamma, float gae_coef, float vf_coef, float entropy_coef, int cross,
+                  float* loss, float* dlogits, float* dcritic, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1369,3 +1369,9 @@ class BatchedMAPPO:
         for _ in range(n_steps):
             self.step()
         return self.last_loss
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# IAC and SEAC: per-agent networks (algorithms/marl/iac.py LoopIAC, seac.py LoopSEAC), mfg_amd/seac.py
+# ---------------------------------------------------------------------------------------------------------------------
+from .seac import AgentNets, BatchedIAC, BatchedSEAC, iac_loss_terms, seac_loss_terms  # noqa: E402,F401
