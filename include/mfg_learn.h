@@ -122,6 +122,51 @@ int mfg_seac_head(const float* logits, const float* critic, int n_agents, int64_
                   const int32_t* n_act, float gamma, float gae_coef, float vf_coef, float entropy_coef, int cross,
                   float* loss, float* dlogits, float* dcritic, void* ws, void* stream);
 
+/* ---- evaluation (mfg_amd/evaluate.py BatchedEvaluator; algorithms/marl/base_ac.py:152-183 eval_loop), mfg_act.hip. */
+
+/* The actor of g stacked RecurrentAC networks (use_agent_embedding = False) for mfg_policy_act, every matrix K-major
+ * (the transpose of the nn.Linear / nn.GRU parameter: wt[net][in][out]), contiguous f32 device arrays:
+ *   action_emb [g][n_max + 1][AE]                          (row 0 = "no action", read like any other row)
+ *   w1t [g][E + AE][E], b1 [g][E];  w3t [g][E][E], b3 [g][E]      (mix.1, mix.3)
+ *   wiht [g][E][3H], bih [g][3H];  whht [g][H][3H], bhh [g][3H]   (gru_actor, gate order r, z, n)
+ *   wat [g][H][H], ba [g][H];  wbt [g][H][n_max], bb [g][n_max]   (action_head.0, action_head.2) */
+typedef struct mfg_actor_weights {
+  const float *action_emb, *w1t, *b1, *w3t, *b3, *wiht, *bih, *whht, *bhh, *wat, *ba, *wbt, *bb;
+} mfg_actor_weights;
+
+/* One acting step of the actor for every row (env b < n_envs, agent i < n_agents), as one kernel, in f32; agent i
+ * uses network i % g (g == 1: shared, g == n_agents: one per agent):
+ *   a_in = prev_done[b] ? -1 : prev_action[b][i];  h_in = prev_done[b] ? 0 : h[b][i]
+ *          (prev_action or prev_done NULL: an episode start for every row; an a_in outside [-1, n_max) counts as -1)
+ *   ax = tanh(cat(emb[b][i], action_emb[a_in + 1]));  x = W3 tanh(W1 ax + b1) + b3
+ *   h' = GRU cell on (x, h_in), mfg_gru_fwd_step's arithmetic                        -> h[b][i], in place
+ *   lg = Wb tanh(Wa h' + ba) + bb                                                    -> logits_out (may be NULL)
+ *   act = greedy ? argmax(lg[:n_act[net]]) (lowest index on ties)
+ *                : mfg_sample_categorical's inversion at u[b][i] over lg[:n_act[net]];
+ *         -1 for non-finite logits or n_act[net] outside [1, n_max]                  -> act_out
+ * emb and h are read at b * *_env + i * *_agent (elements): engine order [B][A][..] and agent-major [A][B][..] both
+ * work in place. prev_action / act_out i32, u f32 and logits_out [..][n_max] (all n_max columns are written) are
+ * [n_envs][n_agents] in engine order; prev_done u8 [n_envs]; n_act i32 [g] (device). u may be NULL with greedy.
+ * Every output element is one k-ordered fmaf chain: deterministic, independent of the launch shape.
+ * -1 (nothing launched) unless 1 <= e_dim <= 128, 1 <= ae_dim <= 32, 1 <= hd <= 128, 1 <= n_max <= 32 and
+ * g in {1, n_agents}. */
+int mfg_policy_act(const float* emb, int64_t emb_env, int64_t emb_agent, int64_t n_envs, int n_agents, int g,
+                   int e_dim, int ae_dim, int hd, int n_max, const mfg_actor_weights* w, const int32_t* n_act,
+                   const int32_t* prev_action, const uint8_t* prev_done, float* h, int64_t h_env, int64_t h_agent,
+                   const float* u, int greedy, int32_t* act_out, float* logits_out, void* stream);
+
+/* eval_loop's bookkeeping after one step, per env b (reward f64 [n_envs][n_agents], done u8 [n_envs] of that step):
+ *   eps_rew[b][i] (f32) += (float) reward[b][i];  len[b] += 1
+ *   if done[b]:  k = count[b]
+ *       if k < n_episodes:  rows[b][k][i] = eps_rew[b][i];  rows[b][k][n_agents] = ((0 + e_0) + e_1) + ... in f32;
+ *                           lengths[b][k] = len[b];  count[b] = k + 1;  if k + 1 == n_episodes: *finished += 1
+ *       eps_rew[b][:] = 0;  len[b] = 0
+ * rows f32 [n_envs][n_episodes][n_agents + 1], lengths / len / count i32, finished i32 (one integer atomic per env
+ * that completes). An env with n_episodes rows keeps stepping and writes no result. */
+int mfg_eval_fold(const double* reward, const uint8_t* done, int64_t n_envs, int n_agents, int n_episodes,
+                  float* eps_rew, int32_t* len, int32_t* count, float* rows, int32_t* lengths, int32_t* finished,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

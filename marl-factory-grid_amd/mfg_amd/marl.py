@@ -1375,3 +1375,14 @@ class BatchedMAPPO:
 # IAC and SEAC: per-agent networks (algorithms/marl/iac.py LoopIAC, seac.py LoopSEAC), mfg_amd/seac.py
 # ---------------------------------------------------------------------------------------------------------------------
 from .seac import AgentNets, BatchedIAC, BatchedSEAC, iac_loss_terms, seac_loss_terms  # noqa: E402,F401
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# evaluation (base_ac.py:152-183 eval_loop) and reference checkpoints, mfg_amd/evaluate.py
+# ---------------------------------------------------------------------------------------------------------------------
+def __getattr__(name):
+    # resolved on first use: evaluate.py imports this module, whichever of the two is imported first
+    if name in ('BatchedEvaluator', 'load_reference_checkpoint'):
+        from . import evaluate
+        return getattr(evaluate, name)
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
