@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/mfg_learn.h"
+#include "mfg_learn_device.h"
 
 namespace {
 
@@ -21,7 +22,6 @@ constexpr int TILE = 32;      // rows per block
 constexpr int WROWS = 8;      // rows per wave
 constexpr int MAX_E = 128, MAX_AE = 32, MAX_H = 128, MAX_ACT = 32;
 
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 __host__ __device__ constexpr int pad4(int x) { return (x + 3) & ~3; }
 
 // acc[c][r] += sum_k in[r][k] wt[k][col[c]] for the wave's WROWS rows (in: LDS rows of stride `ls`, zero padded to a
@@ -98,6 +98,13 @@ struct ActArgs {
   int64_t rows_per_group;
 };
 
+// row q of a group as (env b, agent i): per-agent networks (g > 1) put the agent on blockIdx.y and q is the env; the
+// shared network walks the engine's [B][A] rows
+__device__ __forceinline__ void row_env_agent(int g, int A, int64_t q, int64_t& b, int& i) {
+  if (g > 1) { b = q; i = (int)blockIdx.y; }
+  else { b = q / A; i = (int)(q - b * A); }
+}
+
 __global__ void __launch_bounds__(256) k_policy_act(const ActArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int E = p.E, AE = p.AE, H = p.H, NM = p.n_max, A = p.n_agents;
@@ -129,10 +136,7 @@ __global__ void __launch_bounds__(256) k_policy_act(const ActArgs p) {
     const int64_t q = row0 + r;  // row inside the group
     const bool on = q < p.rows_per_group;
     int64_t b = 0; int i = 0;
-    if (on) {
-      if (p.g > 1) { b = q; i = (int)blockIdx.y; }
-      else { b = q / A; i = (int)(q - b * A); }
-    }
+    if (on) row_env_agent(p.g, A, q, b, i);
     const bool fresh = !p.prev_action || !p.prev_done || p.prev_done[b] != 0;  // episode start
     int a_in = (on && !fresh) ? p.prev_action[b * A + i] : -1;
     if (a_in < -1 || a_in >= NM) a_in = -1;
@@ -187,8 +191,7 @@ __global__ void __launch_bounds__(256) k_policy_act(const ActArgs p) {
         const int64_t q = row0 + wv * WROWS + r;
         if (q < p.rows_per_group) {
           int64_t b; int i;
-          if (p.g > 1) { b = q; i = (int)blockIdx.y; }
-          else { b = q / A; i = (int)(q - b * A); }
+          row_env_agent(p.g, A, q, b, i);
           p.h[b * p.h_env + i * p.h_agent + j] = hn[r];
         }
       }
@@ -210,32 +213,15 @@ __global__ void __launch_bounds__(256) k_policy_act(const ActArgs p) {
     const int64_t q = row0 + tid;
     if (q < p.rows_per_group) {
       int64_t b; int i;
-      if (p.g > 1) { b = q; i = (int)blockIdx.y; }
-      else { b = q / A; i = (int)(q - b * A); }
+      row_env_agent(p.g, A, q, b, i);
       const int64_t row = b * A + i;
       const float* l = bufB + tid * lsB;
       const int n_act = p.n_act[net];
       int pick = -1;
       if (n_act >= 1 && n_act <= NM) {
-        float mx = l[0];
-        for (int a = 1; a < n_act; a++) mx = fmaxf(mx, l[a]);
-        float s = 0.0f;
-        for (int a = 0; a < n_act; a++) s += expf(l[a] - mx);
-        if (s > 0.0f && !isinf(s)) {
-          if (p.greedy) {
-            pick = 0;
-            for (int a = 1; a < n_act; a++)
-              if (l[a] > l[pick]) pick = a;
-          } else {
-            const float thr = p.u[row] * s;
-            float c = 0.0f;
-            pick = n_act - 1;
-            for (int a = 0; a < n_act; a++) {
-              c += expf(l[a] - mx);
-              if (thr < c) { pick = a; break; }
-            }
-          }
-        }
+        float mx, s;
+        row_max_expsum(l, n_act, mx, s);
+        if (s > 0.0f && !isinf(s)) pick = row_pick(l, n_act, mx, s, p.greedy != 0, p.greedy ? 0.0f : p.u[row]);
       }
       p.act_out[row] = pick;
       if (p.logits_out)

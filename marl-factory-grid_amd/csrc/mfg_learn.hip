@@ -9,25 +9,32 @@
 #include <stdint.h>
 #include <algorithm>
 #include "../../include/mfg_learn.h"
+#include "mfg_learn_device.h"
 
 namespace {
 
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // h' = n + z (hp - n), hp = h keep, r = s(gi_r + gh_r), z = s(gi_z + gh_z), n = tanh(gi_n + r gh_n),
-// gh = keep (h W_hh^T) + b_hh (gh0 = h W_hh^T without bias: keep in {0, 1} commutes with the GEMM)
+// gh = keep (h W_hh^T) + b_hh (gh0 = h W_hh^T without bias: keep in {0, 1} commutes with the GEMM).
+// The recurrent bias of row i is bh_all for all rows or (GROUPED) block i / rows_per_group of it, one per network; a
+// template parameter, so the one-bias kernel pays no 64-bit divide and takes no argument for it (an empty struct).
+template <bool GROUPED> struct GruGroups { int64_t rows; };
+template <> struct GruGroups<false> {};
+
+template <bool GROUPED>
 __global__ void __launch_bounds__(256) k_gru_fwd(const float* __restrict__ gi, int64_t gi_row,
-                                                 const float* __restrict__ gh0, const float* __restrict__ bh,
+                                                 const float* __restrict__ gh0, const float* __restrict__ bh_all,
                                                  const float* __restrict__ h, int64_t h_row,
                                                  const float* __restrict__ keep, int64_t keep_row,
                                                  float* __restrict__ h_out, int64_t ho_row, float* __restrict__ hp_o,
                                                  float* __restrict__ r_o, float* __restrict__ z_o,
                                                  float* __restrict__ n_o, float* __restrict__ ghn_o, int64_t sv_row,
-                                                 int64_t n, int hd) {
+                                                 int64_t n, int hd, const GruGroups<GROUPED> grp) {
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n * hd) return;
   const int64_t i = k / hd;
   const int j = (int)(k - i * hd);
+  const float* bh = bh_all;
+  if constexpr (GROUPED) bh += (i / grp.rows) * (int64_t)(3 * hd);
   const float kp = keep[i * keep_row];
   const float* g = gi + i * gi_row;
   const float* q = gh0 + i * (int64_t)(3 * hd);
@@ -136,22 +143,13 @@ __global__ void __launch_bounds__(256) k_sample_cat(const float* __restrict__ lo
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n) return;
   const float* l = logits + r * lrow;
-  float mx = l[0];
-  for (int a = 1; a < n_act; a++) mx = fmaxf(mx, l[a]);
-  float s = 0.0f;
-  for (int a = 0; a < n_act; a++) s += expf(l[a] - mx);
+  float mx, s;
+  row_max_expsum(l, n_act, mx, s);
   if (!(s > 0.0f) || isinf(s)) {  // non-finite logits (NaN / inf): no distribution; -1 lets the caller report it
     out[r] = -1;
     return;
   }
-  const float thr = u[r] * s;
-  float c = 0.0f;
-  int pick = n_act - 1;  // rounding past the last bin picks the last action
-  for (int a = 0; a < n_act; a++) {
-    c += expf(l[a] - mx);
-    if (thr < c) { pick = a; break; }
-  }
-  out[r] = pick;
+  out[r] = row_pick(l, n_act, mx, s, false, u[r]);
 }
 
 }  // namespace
@@ -161,8 +159,22 @@ extern "C" int mfg_gru_fwd_step(const float* gi, int64_t gi_row, const float* gh
                                 float* hp_out, float* r_out, float* z_out, float* n_out, float* ghn_out,
                                 int64_t sv_row, int64_t n, int hd, void* stream) {
   if (n <= 0 || hd <= 0 || n * hd > (int64_t)INT32_MAX * 256) return -1;
-  hipLaunchKernelGGL(k_gru_fwd, dim3(grid_for(n, hd)), dim3(256), 0, (hipStream_t)stream, gi, gi_row, gh0, bh, h,
-                     h_row, keep, keep_row, h_out, ho_row, hp_out, r_out, z_out, n_out, ghn_out, sv_row, n, hd);
+  hipLaunchKernelGGL(k_gru_fwd<false>, dim3(grid_for(n, hd)), dim3(256), 0, (hipStream_t)stream, gi, gi_row, gh0, bh,
+                     h, h_row, keep, keep_row, h_out, ho_row, hp_out, r_out, z_out, n_out, ghn_out, sv_row, n, hd,
+                     GruGroups<false>{});
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int mfg_gru_fwd_step_grouped(const float* gi, int64_t gi_row, const float* gh0, const float* bh,
+                                        int64_t rows_per_group, const float* h, int64_t h_row, const float* keep,
+                                        int64_t keep_row, float* h_out, int64_t ho_row, float* hp_out, float* r_out,
+                                        float* z_out, float* n_out, float* ghn_out, int64_t sv_row, int64_t n, int hd,
+                                        void* stream) {
+  if (n <= 0 || hd <= 0 || rows_per_group <= 0 || n % rows_per_group != 0 || n * hd > (int64_t)INT32_MAX * 256)
+    return -1;
+  hipLaunchKernelGGL(k_gru_fwd<true>, dim3(grid_for(n, hd)), dim3(256), 0, (hipStream_t)stream, gi, gi_row, gh0, bh,
+                     h, h_row, keep, keep_row, h_out, ho_row, hp_out, r_out, z_out, n_out, ghn_out, sv_row, n, hd,
+                     GruGroups<true>{rows_per_group});
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -13,21 +13,12 @@
 #include <stdint.h>
 #include <math.h>
 #include "../../include/mfg_learn.h"
+#include "mfg_learn_device.h"
 
 namespace {
 
 constexpr int MAX_BLOCKS = 1024;  // partials per reduction: the workspace bound (MFG_PPO_WS_BYTES = 2 * 1024 * 8)
 static_assert(2 * MAX_BLOCKS * sizeof(double) == MFG_PPO_WS_BYTES, "workspace bound");
-
-// sum of v over the block's 256 threads, the same tree every run; the result is valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  __syncthreads();  // sh may still be read from a previous call
-  if (lane == 0) sh[wv] = v;
-  __syncthreads();
-  return threadIdx.x == 0 ? ((sh[0] + sh[1]) + (sh[2] + sh[3])) : 0.0;
-}
 
 // R_s = r_s + gamma (1 - d_s) R_{s+1}, R_t = 0 (mappo.py:30-37, f32 in the reference's evaluation order), and per
 // block the f64 sums of (R - c) and (R - c)^2 with the pivot c = reward[0][t-1] (one of the returns: it keeps
@@ -98,16 +89,9 @@ __global__ void __launch_bounds__(256) k_ppo_head(const float* __restrict__ logi
     const float* q = old_logits + i * orow;
     float* dl = dlogits + i * drow;
     const int a = action[i];
-    float mx = l[0], qmx = q[0];
-    for (int j = 1; j < n_act; j++) {
-      mx = fmaxf(mx, l[j]);
-      qmx = fmaxf(qmx, q[j]);
-    }
-    float s = 0.0f, qs = 0.0f;
-    for (int j = 0; j < n_act; j++) {
-      s += expf(l[j] - mx);
-      qs += expf(q[j] - qmx);
-    }
+    float mx, s, qmx, qs;
+    row_max_expsum(l, n_act, mx, s);
+    row_max_expsum(q, n_act, qmx, qs);
     // fmaxf drops a NaN operand, the sums keep it: s and qs are finite and positive exactly when every logit is
     const bool ok = a >= 0 && a < n_act && s > 0.0f && qs > 0.0f && !isinf(s) && !isinf(qs) && !isinf(mx) &&
                     !isinf(qmx);

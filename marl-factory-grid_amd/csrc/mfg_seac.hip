@@ -1,7 +1,7 @@
 // Kernels of the per-agent-network learners (mfg_amd/seac.py BatchedIAC / BatchedSEAC; the reference's
-// algorithms/marl/iac.py and seac.py): obs_proj of packed rows by per-agent weights, the GRU forward step with one
-// recurrent bias per agent block, and the IAC / SEAC loss head (loss, dlogits and dcritic of all networks in one
-// call). fp32 data, f64 accumulation of the loss sums; -ffp-contract=off keeps products and sums separately rounded,
+// algorithms/marl/iac.py and seac.py): obs_proj of packed rows by per-agent weights and the IAC / SEAC loss head
+// (loss, dlogits and dcritic of all networks in one call; the GRU forward step with one recurrent bias per agent
+// block is mfg_learn.hip's k_gru_fwd<true>). fp32 data, f64 accumulation of the loss sums; -ffp-contract=off keeps products and sums separately rounded,
 // as in the tensor code (seac.py seac_loss_terms / iac_loss_terms).
 //
 // Loss head mapping: blockIdx.y = the network; a block takes 256 / (t + 1) whole (network, row) pairs at a time with
@@ -14,21 +14,13 @@
 #include <stdint.h>
 #include <math.h>
 #include "../../include/mfg_learn.h"
+#include "mfg_learn_device.h"
 
 namespace {
 
 constexpr int SEAC_BLOCKS = 256;  // partial pairs per network: MFG_SEAC_WS_BYTES(g) = g * 256 * 2 * 8
 static_assert(MFG_SEAC_WS_BYTES(1) == SEAC_BLOCKS * 2 * sizeof(double), "workspace bound");
 constexpr int PROJ_MAX_CAP = 2048;  // the compacted entries of 4 rows in LDS: 4 * 2048 * 8 B = 64 KiB
-
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  __syncthreads();  // sh may still be read from a previous call
-  if (lane == 0) sh[wv] = v;
-  __syncthreads();
-  return threadIdx.x == 0 ? ((sh[0] + sh[1]) + (sh[2] + sh[3])) : 0.0;
-}
 
 // ---- packed-row projection by per-agent weights. One wave per row r (agent r % G): the row's nonzero entries are
 // compacted once into a wave-private LDS list (every chunk of 64 entries is walked, zero values skipped), then each
@@ -80,44 +72,13 @@ __global__ void __launch_bounds__(256) k_project_grouped(const uint16_t* __restr
   }
 }
 
-// ---- k_gru_fwd of mfg_learn.hip with the recurrent bias of row i taken from block i / rows_per_group
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-__global__ void __launch_bounds__(256) k_gru_fwd_grouped(const float* __restrict__ gi, int64_t gi_row,
-                                                         const float* __restrict__ gh0, const float* __restrict__ bh_all,
-                                                         int64_t rows_per_group, const float* __restrict__ h,
-                                                         int64_t h_row, const float* __restrict__ keep,
-                                                         int64_t keep_row, float* __restrict__ h_out, int64_t ho_row,
-                                                         float* __restrict__ hp_o, float* __restrict__ r_o,
-                                                         float* __restrict__ z_o, float* __restrict__ n_o,
-                                                         float* __restrict__ ghn_o, int64_t sv_row, int64_t n, int hd) {
-  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n * hd) return;
-  const int64_t i = k / hd;
-  const int j = (int)(k - i * hd);
-  const float* bh = bh_all + (i / rows_per_group) * (int64_t)(3 * hd);
-  const float kp = keep[i * keep_row];
-  const float* g = gi + i * gi_row;
-  const float* q = gh0 + i * (int64_t)(3 * hd);
-  const float hp = h ? h[i * h_row + j] * kp : 0.0f;
-  const float ar = q[j] * kp + bh[j], az = q[hd + j] * kp + bh[hd + j], ghn = q[2 * hd + j] * kp + bh[2 * hd + j];
-  const float r = sigm(g[j] + ar);
-  const float z = sigm(g[hd + j] + az);
-  const float nn = tanhf(g[2 * hd + j] + r * ghn);
-  h_out[i * ho_row + j] = nn + z * (hp - nn);
-  const int64_t o = i * sv_row + j;
-  hp_o[o] = hp; r_o[o] = r; z_o[o] = z; n_o[o] = nn; ghn_o[o] = ghn;
-}
-
 // ---- the loss head
 struct Strides { int64_t step, env, agent; };
 
 // max and exp-sum of n logits; false when one of them is not finite (fmaxf drops a NaN operand, the sum keeps it)
 __device__ __forceinline__ bool softmax_stats(const float* __restrict__ l, int n, float& lse) {
-  float mx = l[0];
-  for (int j = 1; j < n; j++) mx = fmaxf(mx, l[j]);
-  float s = 0.0f;
-  for (int j = 0; j < n; j++) s += expf(l[j] - mx);
+  float mx, s;
+  row_max_expsum(l, n, mx, s);
   lse = mx + logf(s);
   return s > 0.0f && !isinf(s) && !isinf(mx);
 }
@@ -260,19 +221,6 @@ extern "C" int mfg_packed_project_grouped(const uint16_t* idx, const float* val,
     return -1;
   hipLaunchKernelGGL(k_project_grouped, dim3((unsigned)((m + 3) / 4)), dim3(256), (size_t)cap * 4 * 2 * sizeof(uint32_t),
                      (hipStream_t)stream, idx, val, m, cap, g, wt, bias, e_dim, k, all ? 1 : 0, out, out_row);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-extern "C" int mfg_gru_fwd_step_grouped(const float* gi, int64_t gi_row, const float* gh0, const float* bh,
-                                        int64_t rows_per_group, const float* h, int64_t h_row, const float* keep,
-                                        int64_t keep_row, float* h_out, int64_t ho_row, float* hp_out, float* r_out,
-                                        float* z_out, float* n_out, float* ghn_out, int64_t sv_row, int64_t n, int hd,
-                                        void* stream) {
-  if (n <= 0 || hd <= 0 || rows_per_group <= 0 || n % rows_per_group != 0 || n * hd > (int64_t)INT32_MAX * 256)
-    return -1;
-  hipLaunchKernelGGL(k_gru_fwd_grouped, dim3((unsigned)((n * hd + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gi,
-                     gi_row, gh0, bh, rows_per_group, h, h_row, keep, keep_row, h_out, ho_row, hp_out, r_out, z_out,
-                     n_out, ghn_out, sv_row, n, hd);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -17,47 +17,26 @@ step is one ``mfg_policy_act`` (the whole actor and the sampling as one kernel, 
 and one ``mfg_eval_fold``; the host reads one integer every ``poll_every`` steps. Which acting path is the default
 follows the measurement.
 """
+import ctypes
 import re
 from pathlib import Path
 
 import torch
 
-from .marl import RecurrentAC, _gru_lib
-from .seac import AgentNets, _seac_lib, _stream
+from . import learn_lib
+from .marl import RecurrentAC
+from .seac import AgentNets
+
+_act_lib = learn_lib.lib  # the former binder's name, for callers written against it
 
 # mfg_policy_act's size limits (include/mfg_learn.h)
 ACT_MAX_E, ACT_MAX_AE, ACT_MAX_H, ACT_MAX_ACT = 128, 32, 128, 32
-_ACT_FIELDS = ('action_emb', 'w1t', 'b1', 'w3t', 'b3', 'wiht', 'bih', 'whht', 'bhh', 'wat', 'ba', 'wbt', 'bb')
-_ACT_LIB = None
-
-
-def _act_lib():
-    """libmfg_hip.so's evaluation kernels (include/mfg_learn.h, csrc/mfg_act.hip), bound once."""
-    global _ACT_LIB
-    if _ACT_LIB is None:
-        import ctypes as C
-        L = _seac_lib()
-        p, i64, i32 = C.c_void_p, C.c_int64, C.c_int
-        L.mfg_policy_act.argtypes = [p, i64, i64, i64, i32, i32, i32, i32, i32, i32, p, p, p, p, p, i64, i64, p, i32, p,
-                                     p, p]
-        L.mfg_policy_act.restype = i32
-        L.mfg_eval_fold.argtypes = [p, p, i64, i32, i32, p, p, p, p, p, p, p]
-        L.mfg_eval_fold.restype = i32
-        _ACT_LIB = L
-    return _ACT_LIB
-
-
-_ACT_STRUCT = None
 
 
 def _weights_struct(w):
     """mfg_actor_weights of an ``actor_weights`` dict, built once per dict."""
-    global _ACT_STRUCT
     if '_struct' not in w:
-        if _ACT_STRUCT is None:
-            import ctypes as C
-            _ACT_STRUCT = type('ActorWeights', (C.Structure,), {'_fields_': [(k, C.c_void_p) for k in _ACT_FIELDS]})
-        w['_struct'] = _ACT_STRUCT(**{k: w[k].data_ptr() for k in _ACT_FIELDS})
+        w['_struct'] = learn_lib.ActorWeights(**{k: w[k].data_ptr() for k in learn_lib.ACTOR_FIELDS})
     return w['_struct']
 
 
@@ -100,20 +79,21 @@ def act_supported(e_dim, ae_dim, hd, n_max):
 
 
 def policy_act(w, emb, emb_strides, n_envs, n_agents, n_act, prev_action, prev_done, h, h_strides, u, act_out,
-               logits_out=None, greedy=False):
+               logits_out=None, greedy=False, check=False):
     """One ``mfg_policy_act`` call on the current stream. w: ``actor_weights``; emb / h: f32 device tensors read at
     env * strides[0] + agent * strides[1] (elements); n_act i32 [g] on the device; prev_action / prev_done None: an
-    episode start. Returns the kernel's return code (-1: sizes outside its limits, nothing launched)."""
+    episode start. Returns the kernel's return code (-1: sizes outside its limits, nothing launched), or with ``check``
+    raises on it."""
     g, k_in, e_dim = w['w1t'].shape
     hd, n_max = w['wbt'].shape[1:]
-    ws = _weights_struct(w)
-    import ctypes as C
-    return _act_lib().mfg_policy_act(
-        emb.data_ptr(), emb_strides[0], emb_strides[1], n_envs, n_agents, g, e_dim, k_in - e_dim, hd, n_max,
-        C.byref(ws), n_act.data_ptr(), None if prev_action is None else prev_action.data_ptr(),
-        None if prev_done is None else prev_done.data_ptr(), h.data_ptr(), h_strides[0], h_strides[1],
-        None if u is None else u.data_ptr(), 1 if greedy else 0, act_out.data_ptr(),
-        None if logits_out is None else logits_out.data_ptr(), _stream(emb.device))
+    ptr = learn_lib.ptr
+    args = (emb.data_ptr(), emb_strides[0], emb_strides[1], n_envs, n_agents, g, e_dim, k_in - e_dim, hd, n_max,
+            ctypes.byref(_weights_struct(w)), n_act.data_ptr(), ptr(prev_action), ptr(prev_done), h.data_ptr(),
+            h_strides[0], h_strides[1], ptr(u), 1 if greedy else 0, act_out.data_ptr(), ptr(logits_out),
+            learn_lib.stream(emb.device))
+    if check:
+        return learn_lib.call('mfg_policy_act', *args)
+    return learn_lib.lib().mfg_policy_act(*args)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -268,10 +248,9 @@ class BatchedEvaluator:
         """AgentNets: obs_proj of the slot's packed rows by every agent's own weights -> _emb [A, B, E]."""
         idx, val = self.pobs.idx[0], self.pobs.val[0]
         if self.dev.type == 'cuda':
-            if _seac_lib().mfg_packed_project_grouped(idx.data_ptr(), val.data_ptr(), self.N, self.pobs.cap, self.A,
-                                                      self._wt.data_ptr(), self._pb.data_ptr(), self.E, self._wt.shape[1],
-                                                      0, self._emb.data_ptr(), self.E, _stream(self.dev)):
-                raise RuntimeError('mfg_packed_project_grouped failed')
+            learn_lib.call('mfg_packed_project_grouped', idx.data_ptr(), val.data_ptr(), self.N, self.pobs.cap, self.A,
+                           self._wt.data_ptr(), self._pb.data_ptr(), self.E, self._wt.shape[1], 0, self._emb.data_ptr(),
+                           self.E, learn_lib.stream(self.dev))
         else:
             self._emb.copy_(self.net.project(self.pobs.idx, self.pobs.val)[:, :, 0])
         if self.check_cap:
@@ -294,10 +273,8 @@ class BatchedEvaluator:
                 emb, es, hs = self.pobs.emb, (A * self.E, self.E), (A * self.H, self.H)
             else:
                 emb, es, hs = self._emb, (self.E, B * self.E), (self.H, B * self.H)
-            rc = policy_act(self.w, emb, es, B, A, self.n_act_dev, None if first else self.act,
-                            None if first else self.done, self.h, hs, u, self.act, logits_out, self.greedy)
-            if rc:
-                raise RuntimeError('mfg_policy_act failed')
+            policy_act(self.w, emb, es, B, A, self.n_act_dev, None if first else self.act,
+                       None if first else self.done, self.h, hs, u, self.act, logits_out, self.greedy, check=True)
             return
         keep = torch.zeros(B, dtype=torch.bool, device=self.dev) if first else ~self.done.bool()
         a_in = torch.where(keep[:, None], self.act.long(), torch.full_like(self.act, -1, dtype=torch.long))
@@ -333,9 +310,8 @@ class BatchedEvaluator:
                 self.act[:, lo:hi] = torch.where(torch.isfinite(lg).all(-1), a, torch.full_like(a, -1))
             return
         if logits.is_cuda and uniform:
-            if _gru_lib().mfg_sample_categorical(logits.data_ptr(), logits.shape[-1], self.n_act[0], u.data_ptr(), self.N,
-                                                 self.act.data_ptr(), _stream(self.dev)):
-                raise RuntimeError('mfg_sample_categorical failed')
+            learn_lib.call('mfg_sample_categorical', logits.data_ptr(), logits.shape[-1], self.n_act[0], u.data_ptr(),
+                           self.N, self.act.data_ptr(), learn_lib.stream(self.dev))
             return
         for lo, hi, n in ([(0, self.A, self.n_act[0])] if uniform else [(i, i + 1, c) for i, c in enumerate(self.n_act)]):
             self.act[:, lo:hi] = sample_inversion(logits[:, lo:hi], u[:, lo:hi], n)
@@ -343,11 +319,9 @@ class BatchedEvaluator:
     # ---- the fold ----
     def _fold(self):
         if self.dev.type == 'cuda':
-            if _act_lib().mfg_eval_fold(self.rew.data_ptr(), self.done.data_ptr(), self.B, self.A, self.n_episodes,
-                                        self.eps_rew.data_ptr(), self.len.data_ptr(), self.count.data_ptr(),
-                                        self.rows.data_ptr(), self.lengths.data_ptr(), self.finished.data_ptr(),
-                                        _stream(self.dev)):
-                raise RuntimeError('mfg_eval_fold failed')
+            learn_lib.call('mfg_eval_fold', self.rew.data_ptr(), self.done.data_ptr(), self.B, self.A, self.n_episodes,
+                           self.eps_rew.data_ptr(), self.len.data_ptr(), self.count.data_ptr(), self.rows.data_ptr(),
+                           self.lengths.data_ptr(), self.finished.data_ptr(), learn_lib.stream(self.dev))
         else:
             eval_fold(self.rew, self.done, self.n_episodes, self.eps_rew, self.len, self.count, self.rows, self.lengths,
                       self.finished)

@@ -31,6 +31,11 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.distributions import Categorical
 
+from . import learn_lib
+
+# the names of the former per-unit binders: callers written against them get the one binding
+_gru_lib = _ppo_lib = learn_lib.lib
+
 
 SPLIT_ROWS = 2048  # rows per split of a tall-K weight-gradient GEMM (_tall_tn)
 
@@ -329,54 +334,27 @@ def _packed_grads(idx, val, g, k):
     if not (g.is_cuda and idx.dtype == torch.uint16) or k > _DENSIFY_MAX_K:
         # (k past the densify kernel's wave-private LDS row: the same dense rows by scatter_add on the device)
         return _packed_weight_grad(idx.long(), val, g, k).t(), g.sum(0)
-    L, st = _gru_lib(), torch.cuda.current_stream(g.device).cuda_stream
+    st = learn_lib.stream(g.device)
     idx, val = idx.contiguous(), val.contiguous()
     gw = None
     step = max(1, (1 << 27) // max(k, 1))
     for r0 in range(0, idx.shape[0], step):
         rows = min(step, idx.shape[0] - r0)
         d = torch.empty((rows, k), dtype=g.dtype, device=g.device)
-        if L.mfg_packed_densify(idx[r0].data_ptr(), val[r0].data_ptr(), rows, idx.shape[1], k, d.data_ptr(), k, st):
-            raise RuntimeError('mfg_packed_densify failed')
+        learn_lib.call('mfg_packed_densify', idx[r0].data_ptr(), val[r0].data_ptr(), rows, idx.shape[1], k,
+                       d.data_ptr(), k, st)
         part = _tall_tn(g[r0:r0 + rows], d)  # [E, k]
         gw = part if gw is None else gw + part
     return gw, g.sum(0)
 
 
-_GRU_LIB = None
 _DENSIFY_MAX_K = 4096  # mfg_packed_densify's bound on the dense row length (include/mfg_learn.h)
-
-
-def _gru_lib():
-    """libmfg_hip.so's learner kernels (include/mfg_learn.h), bound once."""
-    global _GRU_LIB
-    if _GRU_LIB is None:
-        import ctypes as C
-        from .engine import load_lib
-        L = load_lib()
-        p, i64 = C.c_void_p, C.c_int64
-        L.mfg_gru_fwd_step.argtypes = [p, i64, p, p, p, i64, p, i64, p, i64, p, p, p, p, p, i64, i64, C.c_int, p]
-        L.mfg_gru_fwd_step.restype = C.c_int
-        L.mfg_gru_bwd_step.argtypes = [p, i64, p, p, i64, p, p, p, p, p, i64, p, i64, p, i64, p, i64, C.c_int, p]
-        L.mfg_gru_bwd_step.restype = C.c_int
-        L.mfg_packed_densify.argtypes = [p, p, i64, C.c_int, C.c_int, p, i64, p]
-        L.mfg_packed_densify.restype = C.c_int
-        L.mfg_packed_project.argtypes = [p, p, i64, C.c_int, p, p, C.c_int, C.c_int, p, i64, p]
-        L.mfg_packed_project.restype = C.c_int
-        L.mfg_sample_categorical.argtypes = [p, i64, C.c_int, p, i64, p, p]
-        L.mfg_sample_categorical.restype = C.c_int
-        _GRU_LIB = L
-    return _GRU_LIB
 
 
 def _use_gru_kernels(x):
     """The learner's GRU window runs its elementwise steps as HIP kernels on the GPU (fp32); CPU tensors take the
     tensor code (the same formulas)."""
     return x.is_cuda and x.dtype == torch.float32
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 class _GRUWindow(torch.autograd.Function):
@@ -399,7 +377,7 @@ class _GRUWindow(torch.autograd.Function):
         gi = torch.addmm(bi, x.reshape(n * t, i_dim), wi.t()).view(n, t, -1)
         outs, saved = [], []
         if _use_gru_kernels(x):  # per step: the recurrent GEMM + one fused elementwise kernel (mfg_gru_fwd_step)
-            L, st = _gru_lib(), torch.cuda.current_stream(x.device).cuda_stream
+            st = learn_lib.stream(x.device)
             keep = keep.contiguous()
             g_all = gi.shape[-1]
             for (h, wh, bh, lo, hd) in ((h0a, wha, bha, 0, ha_dim), (h0c, whc, bhc, 3 * ha_dim, hc_dim)):
@@ -409,13 +387,11 @@ class _GRUWindow(torch.autograd.Function):
                 hcur, h_row = h.contiguous(), hd
                 for s in range(t):
                     gh0 = hcur @ wh.t()
-                    rc = L.mfg_gru_fwd_step(gi[:, s, lo:].data_ptr(), t * g_all, gh0.data_ptr(), bh.data_ptr(),
-                                            hcur.data_ptr(), h_row, keep[:, s].data_ptr(), t, hs[:, s].data_ptr(),
-                                            t * hd, sv[0, :, s].data_ptr(), sv[1, :, s].data_ptr(),
-                                            sv[2, :, s].data_ptr(), sv[3, :, s].data_ptr(), sv[4, :, s].data_ptr(),
-                                            t * hd, n, hd, st)
-                    if rc:
-                        raise RuntimeError('mfg_gru_fwd_step failed')
+                    learn_lib.call('mfg_gru_fwd_step', gi[:, s, lo:].data_ptr(), t * g_all, gh0.data_ptr(),
+                                   bh.data_ptr(), hcur.data_ptr(), h_row, keep[:, s].data_ptr(), t,
+                                   hs[:, s].data_ptr(), t * hd, sv[0, :, s].data_ptr(), sv[1, :, s].data_ptr(),
+                                   sv[2, :, s].data_ptr(), sv[3, :, s].data_ptr(), sv[4, :, s].data_ptr(), t * hd, n,
+                                   hd, st)
                     hcur, h_row = hs[:, s], t * hd
                 outs.append(hs)
                 saved += list(sv.unbind(0))
@@ -453,7 +429,7 @@ class _GRUWindow(torch.autograd.Function):
         for gi_idx, (dout, wh, hd) in enumerate(((douta, wha, ha_dim), (doutc, whc, hc_dim))):
             hps, rs, zs, ns, ghns = saved[5 * gi_idx:5 * gi_idx + 5]
             if gpu:  # per step: one fused elementwise kernel (mfg_gru_bwd_step) + the recurrent GEMM
-                L, st = _gru_lib(), torch.cuda.current_stream(x.device).cuda_stream
+                st = learn_lib.stream(x.device)
                 dgi = dgi_all[:, :, 3 * ha_dim * gi_idx:]
                 dgh = torch.empty((n, t, 3 * hd), dtype=x.dtype, device=x.device)
                 dout = None if dout is None else dout.contiguous()
@@ -461,14 +437,11 @@ class _GRUWindow(torch.autograd.Function):
                 dhp = None
                 for s in range(t - 1, -1, -1):
                     dhz = torch.empty((n, hd), dtype=x.dtype, device=x.device)
-                    rc = L.mfg_gru_bwd_step(None if dout is None else dout[:, s].data_ptr(), t * hd, _ptr(dhp),
-                                            None if dhp is None else keep[:, s + 1].data_ptr(), t,
-                                            rs[:, s].data_ptr(), zs[:, s].data_ptr(), ns[:, s].data_ptr(),
-                                            ghns[:, s].data_ptr(), hps[:, s].data_ptr(), sv_row,
-                                            dgi[:, s].data_ptr(), t * g_all, dgh[:, s].data_ptr(), t * 3 * hd,
-                                            dhz.data_ptr(), n, hd, st)
-                    if rc:
-                        raise RuntimeError('mfg_gru_bwd_step failed')
+                    learn_lib.call('mfg_gru_bwd_step', None if dout is None else dout[:, s].data_ptr(), t * hd,
+                                   learn_lib.ptr(dhp), None if dhp is None else keep[:, s + 1].data_ptr(), t,
+                                   rs[:, s].data_ptr(), zs[:, s].data_ptr(), ns[:, s].data_ptr(),
+                                   ghns[:, s].data_ptr(), hps[:, s].data_ptr(), sv_row, dgi[:, s].data_ptr(),
+                                   t * g_all, dgh[:, s].data_ptr(), t * 3 * hd, dhz.data_ptr(), n, hd, st)
                     dhp = torch.addmm(dhz, dgh[:, s], wh)
                 dgh2 = dgh.reshape(n * t, 3 * hd)
                 grads.append((_tall_tn(dgh2, hps.reshape(n * t, hd)), dgh2.sum(0)))
@@ -553,7 +526,7 @@ class _GRUWindowSavedT(torch.autograd.Function):
         t, n = keep.shape
         ha_dim, hc_dim = wha.shape[1], whc.shape[1]
         g_all = 3 * (ha_dim + hc_dim)
-        L, st = _gru_lib(), torch.cuda.current_stream(x.device).cuda_stream
+        st = learn_lib.stream(x.device)
         dgi_all = torch.empty((t, n, g_all), dtype=x.dtype, device=x.device)
         grads = []
         for gidx, (dout, wh, hd) in enumerate(((douta, wha, ha_dim), (doutc, whc, hc_dim))):
@@ -564,13 +537,11 @@ class _GRUWindowSavedT(torch.autograd.Function):
             dhp = None
             for s in range(t - 1, -1, -1):
                 dhz = torch.empty((n, hd), dtype=x.dtype, device=x.device)
-                rc = L.mfg_gru_bwd_step(None if dout is None else dout[s].data_ptr(), hd, _ptr(dhp),
-                                        None if dhp is None else keep[s + 1].data_ptr(), 1,
-                                        rs[s].data_ptr(), zs[s].data_ptr(), ns[s].data_ptr(), ghns[s].data_ptr(),
-                                        hps[s].data_ptr(), hd, dgi_all[s, :, lo:].data_ptr(), g_all,
-                                        dgh[s].data_ptr(), 3 * hd, dhz.data_ptr(), n, hd, st)
-                if rc:
-                    raise RuntimeError('mfg_gru_bwd_step failed')
+                learn_lib.call('mfg_gru_bwd_step', None if dout is None else dout[s].data_ptr(), hd,
+                               learn_lib.ptr(dhp), None if dhp is None else keep[s + 1].data_ptr(), 1,
+                               rs[s].data_ptr(), zs[s].data_ptr(), ns[s].data_ptr(), ghns[s].data_ptr(),
+                               hps[s].data_ptr(), hd, dgi_all[s, :, lo:].data_ptr(), g_all, dgh[s].data_ptr(), 3 * hd,
+                               dhz.data_ptr(), n, hd, st)
                 dhp = torch.addmm(dhz, dgh[s], wh)
             dgh2 = dgh.view(t * n, 3 * hd)
             grads.append((_tall_tn(dgh2, hps.reshape(t * n, hd)), dgh2.sum(0)))
@@ -791,18 +762,16 @@ class BatchedA2C:
         net, N, T = self.net, self.N, self.T
         ga, gc = net.gru_actor, net.gru_critic
         gi = torch.addmm(torch.cat([ga.bias_ih_l0, gc.bias_ih_l0]), x, torch.cat([ga.weight_ih_l0, gc.weight_ih_l0]).t())
-        L, st = _gru_lib(), torch.cuda.current_stream(self.dev).cuda_stream
+        st = learn_lib.stream(self.dev)
         lo = 0
         for (h, gru, hs, sv) in ((self.ha, ga, self.hs_a, self.sv_a), (self.hc, gc, self.hs_c, self.sv_c)):
             hd = hs.shape[-1]
             h2 = h[:, 0]
             gh0 = h2 @ gru.weight_hh_l0.t()
-            rc = L.mfg_gru_fwd_step(gi[:, lo:].data_ptr(), gi.shape[1], gh0.data_ptr(), gru.bias_hh_l0.data_ptr(),
-                                    h2.data_ptr(), hd, self._one.data_ptr(), 0, hs[t].data_ptr(), hd,
-                                    sv[0, t].data_ptr(), sv[1, t].data_ptr(), sv[2, t].data_ptr(), sv[3, t].data_ptr(),
-                                    sv[4, t].data_ptr(), hd, N, hd, st)
-            if rc:
-                raise RuntimeError('mfg_gru_fwd_step failed')
+            learn_lib.call('mfg_gru_fwd_step', gi[:, lo:].data_ptr(), gi.shape[1], gh0.data_ptr(),
+                           gru.bias_hh_l0.data_ptr(), h2.data_ptr(), hd, self._one.data_ptr(), 0, hs[t].data_ptr(), hd,
+                           sv[0, t].data_ptr(), sv[1, t].data_ptr(), sv[2, t].data_ptr(), sv[3, t].data_ptr(),
+                           sv[4, t].data_ptr(), hd, N, hd, st)
             lo += 3 * hd
 
     def _sample(self, logits, t):
@@ -818,11 +787,8 @@ class BatchedA2C:
             return
         logits = logits.contiguous()
         self._u.uniform_()
-        rc = _gru_lib().mfg_sample_categorical(logits.data_ptr(), logits.stride(0), logits.shape[1],
-                                               self._u.data_ptr(), self.N, self.act[t].data_ptr(),
-                                               torch.cuda.current_stream(self.dev).cuda_stream)
-        if rc:
-            raise RuntimeError('mfg_sample_categorical failed')
+        learn_lib.call('mfg_sample_categorical', logits.data_ptr(), logits.stride(0), logits.shape[1],
+                       self._u.data_ptr(), self.N, self.act[t].data_ptr(), learn_lib.stream(self.dev))
 
     def _policy_step(self, t):
         if not self.act_graph:
@@ -977,11 +943,9 @@ class BatchedA2C:
         if not pb.idx.is_cuda:
             pb.emb[0].copy_(_project_dense(pb.idx[0], pb.val[0], self.net.obs_proj))
             return
-        rc = _gru_lib().mfg_packed_project(pb.idx[0].data_ptr(), pb.val[0].data_ptr(), self.N, pb.cap, pb.wt.data_ptr(),
-                                           pb.bias.data_ptr(), pb.E, pb.kdim, pb.emb[0].data_ptr(), pb.E,
-                                           torch.cuda.current_stream(self.dev).cuda_stream)
-        if rc:
-            raise RuntimeError('mfg_packed_project failed')
+        learn_lib.call('mfg_packed_project', pb.idx[0].data_ptr(), pb.val[0].data_ptr(), self.N, pb.cap,
+                       pb.wt.data_ptr(), pb.bias.data_ptr(), pb.E, pb.kdim, pb.emb[0].data_ptr(), pb.E,
+                       learn_lib.stream(self.dev))
 
     def train(self, n_updates):
         for _ in range(n_updates * self.T):
@@ -992,23 +956,7 @@ class BatchedA2C:
 # ---------------------------------------------------------------------------------------------------------------------
 # MAPPO: the reference's PPO learner on the same shared RecurrentAC (algorithms/marl/mappo.py LoopMAPPO)
 # ---------------------------------------------------------------------------------------------------------------------
-_PPO_LIB = None
 _PPO_WS_BYTES = 16384  # MFG_PPO_WS_BYTES (include/mfg_learn.h)
-
-
-def _ppo_lib():
-    """libmfg_hip.so's PPO loss head (include/mfg_learn.h, csrc/mfg_ppo.hip), bound once."""
-    global _PPO_LIB
-    if _PPO_LIB is None:
-        import ctypes as C
-        L = _gru_lib()
-        p, i64, f32 = C.c_void_p, C.c_int64, C.c_float
-        L.mfg_mc_returns.argtypes = [p, i64, p, i64, i64, C.c_int, f32, p, i64, p, p, p]
-        L.mfg_mc_returns.restype = C.c_int
-        L.mfg_ppo_head.argtypes = [p, i64, p, i64, p, p, p, p, i64, C.c_int, f32, f32, f32, p, p, i64, p, p, p]
-        L.mfg_ppo_head.restype = C.c_int
-        _PPO_LIB = L
-    return _PPO_LIB
 
 
 def monte_carlo_returns(reward, done, gamma):
@@ -1057,7 +1005,7 @@ class _PPOHead(torch.autograd.Function):
     def forward(ctx, logits, critic, old_logits, actions, reward, done, gamma, entropy_coef, vf_coef, clip_range):
         n, t, n_act = logits.shape
         dev = logits.device
-        L, st = _ppo_lib(), torch.cuda.current_stream(dev).cuda_stream
+        st = learn_lib.stream(dev)
         lg = logits.detach().reshape(n * t, n_act).float().contiguous()
         old = old_logits.reshape(n * t, n_act).float().contiguous()
         cr = critic.detach().reshape(n * t).float().contiguous()
@@ -1066,16 +1014,14 @@ class _PPOHead(torch.autograd.Function):
         ret = torch.empty((n, t), dtype=torch.float32, device=dev)
         stats = torch.empty(2, dtype=torch.float64, device=dev)
         ws = torch.empty(_PPO_WS_BYTES // 8, dtype=torch.float64, device=dev)
-        if L.mfg_mc_returns(rew.data_ptr(), t, dn.data_ptr(), t, n, t, gamma, ret.data_ptr(), t, stats.data_ptr(),
-                            ws.data_ptr(), st):
-            raise RuntimeError('mfg_mc_returns failed (a minibatch needs at least two elements)')
+        learn_lib.call('mfg_mc_returns', rew.data_ptr(), t, dn.data_ptr(), t, n, t, gamma, ret.data_ptr(), t,
+                       stats.data_ptr(), ws.data_ptr(), st)  # (fails on a minibatch of fewer than two elements)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         dlogits = torch.empty((n * t, n_act), dtype=torch.float32, device=dev)
         dcritic = torch.empty(n * t, dtype=torch.float32, device=dev)
-        if L.mfg_ppo_head(lg.data_ptr(), n_act, old.data_ptr(), n_act, cr.data_ptr(), act.data_ptr(), ret.data_ptr(),
-                          stats.data_ptr(), n * t, n_act, clip_range, vf_coef, entropy_coef, loss.data_ptr(),
-                          dlogits.data_ptr(), n_act, dcritic.data_ptr(), ws.data_ptr(), st):
-            raise RuntimeError('mfg_ppo_head failed')
+        learn_lib.call('mfg_ppo_head', lg.data_ptr(), n_act, old.data_ptr(), n_act, cr.data_ptr(), act.data_ptr(),
+                       ret.data_ptr(), stats.data_ptr(), n * t, n_act, clip_range, vf_coef, entropy_coef,
+                       loss.data_ptr(), dlogits.data_ptr(), n_act, dcritic.data_ptr(), ws.data_ptr(), st)
         ctx.save_for_backward(dlogits.view(n, t, n_act), dcritic.view(n, t))
         return loss
 
@@ -1358,11 +1304,9 @@ class BatchedMAPPO:
         if not pb.idx.is_cuda:
             pb.emb[k].copy_(_project_dense(pb.idx[k], pb.val[k], self.net.obs_proj))
             return
-        rc = _gru_lib().mfg_packed_project(pb.idx[k].data_ptr(), pb.val[k].data_ptr(), self.N, pb.cap, pb.wt.data_ptr(),
-                                           pb.bias.data_ptr(), pb.E, pb.kdim, pb.emb[k].data_ptr(), pb.E,
-                                           torch.cuda.current_stream(self.dev).cuda_stream)
-        if rc:
-            raise RuntimeError('mfg_packed_project failed')
+        learn_lib.call('mfg_packed_project', pb.idx[k].data_ptr(), pb.val[k].data_ptr(), self.N, pb.cap,
+                       pb.wt.data_ptr(), pb.bias.data_ptr(), pb.E, pb.kdim, pb.emb[k].data_ptr(), pb.E,
+                       learn_lib.stream(self.dev))
 
     def train(self, n_steps):
         """n_steps env-steps (with the learn calls that fall into them); returns the last minibatch loss."""

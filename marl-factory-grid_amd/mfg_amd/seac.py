@@ -21,37 +21,17 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.distributions import Categorical
 
-from .marl import RecurrentAC, _gru_lib, _ptr, _use_gru_kernels, compute_advantages
+from . import learn_lib
+from .marl import RecurrentAC, _use_gru_kernels, compute_advantages
+
+_seac_lib = learn_lib.lib  # the former binder's name, for callers written against it
 
 _PAD_KEYS = ('action_emb.weight', 'action_head.2.weight', 'action_head.2.bias')  # rows follow the action count
-_SEAC_LIB = None
-
-
-def _seac_lib():
-    """libmfg_hip.so's per-agent-network kernels (include/mfg_learn.h, csrc/mfg_seac.hip), bound once."""
-    global _SEAC_LIB
-    if _SEAC_LIB is None:
-        import ctypes as C
-        L = _gru_lib()
-        p, i64, f32, i32 = C.c_void_p, C.c_int64, C.c_float, C.c_int
-        L.mfg_packed_project_grouped.argtypes = [p, p, i64, i32, i32, p, p, i32, i32, i32, p, i64, p]
-        L.mfg_packed_project_grouped.restype = i32
-        L.mfg_gru_fwd_step_grouped.argtypes = [p, i64, p, p, i64, p, i64, p, i64, p, i64, p, p, p, p, p, i64, i64, i32, p]
-        L.mfg_gru_fwd_step_grouped.restype = i32
-        L.mfg_seac_head.argtypes = [p, p, i32, i64, i32, i32, p, i64, i64, i64, p, i64, i64, i64, p, i64, i64, i64, p,
-                                    f32, f32, f32, f32, i32, p, p, p, p, p]
-        L.mfg_seac_head.restype = i32
-        _SEAC_LIB = L
-    return _SEAC_LIB
 
 
 def seac_ws_bytes(n_agents):
     """MFG_SEAC_WS_BYTES(g) (include/mfg_learn.h)."""
     return 4096 * n_agents
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def _blin(x, w, b):
@@ -72,8 +52,8 @@ def _dense_rows(idx, val, k):
     m, cap = idx.shape
     if val.is_cuda and idx.dtype == torch.uint16 and k <= 4096:
         d = torch.empty((m, k), dtype=torch.float32, device=val.device)
-        if _gru_lib().mfg_packed_densify(idx.data_ptr(), val.data_ptr(), m, cap, k, d.data_ptr(), k, _stream(val.device)):
-            raise RuntimeError('mfg_packed_densify failed')
+        learn_lib.call('mfg_packed_densify', idx.data_ptr(), val.data_ptr(), m, cap, k, d.data_ptr(), k,
+                       learn_lib.stream(val.device))
         return d
     d = torch.zeros((m, k), dtype=torch.float32, device=val.device)
     ix = idx.view(torch.int16).long() & 0xFFFF if idx.dtype == torch.uint16 else idx.long()
@@ -103,13 +83,12 @@ class _GroupedProj(torch.autograd.Function):
         shape = (A, A, B, S, E) if all_ else (A, B, S, E)
         if val.is_cuda:
             out = torch.empty(shape, dtype=torch.float32, device=val.device)
-            L, st = _seac_lib(), _stream(val.device)
+            st = learn_lib.stream(val.device)
             idx, val, b = idx.contiguous(), val.contiguous(), bias.detach().contiguous()
             for s in range(S):
-                if L.mfg_packed_project_grouped(idx[s].data_ptr(), val[s].data_ptr(), B * A, cap, A, wt.data_ptr(),
-                                                b.data_ptr(), E, k, 1 if all_ else 0,
-                                                out.view(-1)[s * E:].data_ptr(), S * E, st):
-                    raise RuntimeError('mfg_packed_project_grouped failed')
+                learn_lib.call('mfg_packed_project_grouped', idx[s].data_ptr(), val[s].data_ptr(), B * A, cap, A,
+                               wt.data_ptr(), b.data_ptr(), E, k, 1 if all_ else 0, out.view(-1)[s * E:].data_ptr(),
+                               S * E, st)
             return out
         d = _dense_rows(_agent_major(idx).view(-1, cap), _agent_major(val).view(-1, cap), k).view(A, B * S, k)
         if all_:
@@ -152,7 +131,7 @@ class _GRUWindowG(torch.autograd.Function):
         hd = g3 // 3
         whT = wh.transpose(1, 2)
         if _use_gru_kernels(gi):
-            L, st = _seac_lib(), _stream(gi.device)
+            st = learn_lib.stream(gi.device)
             if gi.stride(3) != 1 or gi.stride(2) < g3 or gi.stride(1) != T * gi.stride(2) or \
                     gi.stride(0) != n * gi.stride(1):
                 gi = gi.contiguous()  # (a column slice of both GRUs' gates is read in place)
@@ -162,14 +141,11 @@ class _GRUWindowG(torch.autograd.Function):
             hcur, h_row = h0.contiguous(), hd
             for s in range(T):
                 gh0 = torch.bmm(hcur, whT)  # [A, n, 3hd]
-                rc = L.mfg_gru_fwd_step_grouped(gi[:, :, s].data_ptr(), gi.stride(1), gh0.data_ptr(), bh.data_ptr(), n,
-                                                hcur.data_ptr(), h_row, keep[:, :, s].data_ptr(), T,
-                                                hs[:, :, s].data_ptr(), T * hd, sv[0, :, :, s].data_ptr(),
-                                                sv[1, :, :, s].data_ptr(), sv[2, :, :, s].data_ptr(),
-                                                sv[3, :, :, s].data_ptr(), sv[4, :, :, s].data_ptr(), T * hd, A * n, hd,
-                                                st)
-                if rc:
-                    raise RuntimeError('mfg_gru_fwd_step_grouped failed')
+                learn_lib.call('mfg_gru_fwd_step_grouped', gi[:, :, s].data_ptr(), gi.stride(1), gh0.data_ptr(),
+                               bh.data_ptr(), n, hcur.data_ptr(), h_row, keep[:, :, s].data_ptr(), T,
+                               hs[:, :, s].data_ptr(), T * hd, sv[0, :, :, s].data_ptr(), sv[1, :, :, s].data_ptr(),
+                               sv[2, :, :, s].data_ptr(), sv[3, :, :, s].data_ptr(), sv[4, :, :, s].data_ptr(), T * hd,
+                               A * n, hd, st)
                 hcur, h_row = hs[:, :, s], T * hd
             saved = list(sv.unbind(0))
         else:
@@ -198,19 +174,16 @@ class _GRUWindowG(torch.autograd.Function):
         dgi = torch.empty((A, n, T, 3 * hd), dtype=hps.dtype, device=hps.device)
         dgh = torch.empty_like(dgi)
         if _use_gru_kernels(hps):
-            L, st = _gru_lib(), _stream(hps.device)
+            st = learn_lib.stream(hps.device)
             dout = dout.contiguous()
             dhp = None
             for s in range(T - 1, -1, -1):
                 dhz = torch.empty((A, n, hd), dtype=hps.dtype, device=hps.device)
-                rc = L.mfg_gru_bwd_step(dout[:, :, s].data_ptr(), T * hd, _ptr(dhp),
-                                        None if dhp is None else keep[:, :, s + 1].data_ptr(), T,
-                                        rs[:, :, s].data_ptr(), zs[:, :, s].data_ptr(), ns[:, :, s].data_ptr(),
-                                        ghns[:, :, s].data_ptr(), hps[:, :, s].data_ptr(), T * hd,
-                                        dgi[:, :, s].data_ptr(), T * 3 * hd, dgh[:, :, s].data_ptr(), T * 3 * hd,
-                                        dhz.data_ptr(), A * n, hd, st)
-                if rc:
-                    raise RuntimeError('mfg_gru_bwd_step failed')
+                learn_lib.call('mfg_gru_bwd_step', dout[:, :, s].data_ptr(), T * hd, learn_lib.ptr(dhp),
+                               None if dhp is None else keep[:, :, s + 1].data_ptr(), T, rs[:, :, s].data_ptr(),
+                               zs[:, :, s].data_ptr(), ns[:, :, s].data_ptr(), ghns[:, :, s].data_ptr(),
+                               hps[:, :, s].data_ptr(), T * hd, dgi[:, :, s].data_ptr(), T * 3 * hd,
+                               dgh[:, :, s].data_ptr(), T * 3 * hd, dhz.data_ptr(), A * n, hd, st)
                 dhp = torch.baddbmm(dhz, dgh[:, :, s], wh)
         else:
             carry = torch.zeros((A, n, hd), dtype=hps.dtype, device=hps.device)
@@ -467,11 +440,10 @@ class _SEACHead(torch.autograd.Function):
         loss = torch.empty(A, dtype=torch.float32, device=dev)
         dlogits, dcritic = torch.empty_like(lg), torch.empty_like(cr)
         ws = torch.empty(seac_ws_bytes(A) // 8, dtype=torch.float64, device=dev)
-        if _seac_lib().mfg_seac_head(lg.data_ptr(), cr.data_ptr(), A, B, t, n_max, action.data_ptr(), *a_str,
-                                     reward.data_ptr(), *r_str, done.data_ptr(), *d_str, n_act.data_ptr(), gamma,
-                                     gae_coef, vf_coef, entropy_coef, 1 if cross else 0, loss.data_ptr(),
-                                     dlogits.data_ptr(), dcritic.data_ptr(), ws.data_ptr(), _stream(dev)):
-            raise RuntimeError('mfg_seac_head failed')
+        learn_lib.call('mfg_seac_head', lg.data_ptr(), cr.data_ptr(), A, B, t, n_max, action.data_ptr(), *a_str,
+                       reward.data_ptr(), *r_str, done.data_ptr(), *d_str, n_act.data_ptr(), gamma, gae_coef, vf_coef,
+                       entropy_coef, 1 if cross else 0, loss.data_ptr(), dlogits.data_ptr(), dcritic.data_ptr(),
+                       ws.data_ptr(), learn_lib.stream(dev))
         ctx.save_for_backward(dlogits, dcritic)
         ctx.A, ctx.cross = A, cross
         return loss
@@ -613,13 +585,11 @@ class BatchedIAC:
         else:
             logits = logits.contiguous()
             self._u.uniform_()
-            L, st = _gru_lib(), _stream(self.dev)
+            st = learn_lib.stream(self.dev)
             blocks = [(0, A * B, self.n_max)] if self.uniform else [(g * B, B, self.n_act[g]) for g in range(A)]
             for r0, rows, n in blocks:
-                if L.mfg_sample_categorical(logits.view(A * B, -1)[r0].data_ptr(), logits.shape[-1], n,
-                                            self._u.view(-1)[r0:].data_ptr(), rows,
-                                            self._act_am.view(-1)[r0:].data_ptr(), st):
-                    raise RuntimeError('mfg_sample_categorical failed')
+                learn_lib.call('mfg_sample_categorical', logits.view(A * B, -1)[r0].data_ptr(), logits.shape[-1], n,
+                               self._u.view(-1)[r0:].data_ptr(), rows, self._act_am.view(-1)[r0:].data_ptr(), st)
         self.act[t].copy_(self._act_am.t())
 
     def window(self):

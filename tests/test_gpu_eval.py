@@ -19,7 +19,8 @@ import torch
 from conftest import gpu_available
 import eval_ref as R
 import mfg_amd.evaluate as EV
-from mfg_amd.marl import AgentNets, RecurrentAC, _gru_lib
+from mfg_amd import learn_lib
+from mfg_amd.marl import AgentNets, RecurrentAC
 
 pytestmark = pytest.mark.gpu
 FIGURES = {}
@@ -140,8 +141,8 @@ def sampler(logits, u, n_act, g):
     for i in range(A):
         lg, ui = logits[:, i].contiguous(), u[:, i].contiguous().cuda()
         o = torch.zeros(B, dtype=torch.int32, device='cuda')
-        assert _gru_lib().mfg_sample_categorical(lg.data_ptr(), n_max, n_act[i % g], ui.data_ptr(), B, o.data_ptr(),
-                                                 _stream()) == 0
+        assert learn_lib.lib().mfg_sample_categorical(lg.data_ptr(), n_max, n_act[i % g], ui.data_ptr(), B,
+                                                      o.data_ptr(), _stream()) == 0
         out[:, i] = o
     return out
 
@@ -274,7 +275,7 @@ def test_eval_fold_kernel_is_the_float32_loop(A, B):
     rows = rb[guard:-guard].view(B, n_ep, A + 1)
     lengths, fin = torch.zeros((B, n_ep), dtype=torch.int32, device=dev), torch.zeros((), dtype=torch.int32, device=dev)
     rw, dn = rewards.to(dev), dones.to(dev)
-    L = EV._act_lib()
+    L = learn_lib.lib()
     for t in range(steps):
         assert L.mfg_eval_fold(rw[t].data_ptr(), dn[t].data_ptr(), B, A, n_ep, eps.data_ptr(), ln.data_ptr(),
                                cnt.data_ptr(), rows.data_ptr(), lengths.data_ptr(), fin.data_ptr(), _stream()) == 0

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import mfg_amd.marl as M
+from mfg_amd import learn_lib
 from test_mappo import check_loss_and_grads, hyper, load_case, pack
 
 pytestmark = pytest.mark.gpu
@@ -38,8 +39,8 @@ def _mc(reward, done, gamma, pad=3):
     ret = torch.full((n, t + pad), -5.0, device='cuda')
     stats = torch.zeros(2, dtype=torch.float64, device='cuda')
     ws = _ws()
-    rc = M._ppo_lib().mfg_mc_returns(r.data_ptr(), t + pad, d.data_ptr(), t + pad, n, t, gamma, ret.data_ptr(),
-                                     t + pad, stats.data_ptr(), ws.data_ptr(), _stream())
+    rc = learn_lib.lib().mfg_mc_returns(r.data_ptr(), t + pad, d.data_ptr(), t + pad, n, t, gamma, ret.data_ptr(),
+                                        t + pad, stats.data_ptr(), ws.data_ptr(), _stream())
     torch.cuda.synchronize()
     return rc, ret[:, :t].clone(), stats, ret[:, t:]
 
@@ -132,7 +133,7 @@ def kernel_head(x, pad=3, act=None, logits=None):
     """mfg_mc_returns + mfg_ppo_head on padded logit rows: (rc, loss, dlogits, dcritic, dlogits' pad columns)."""
     n, t = x['n'], x['t']
     m, n_act = x['logits'].shape
-    L = M._ppo_lib()
+    L = learn_lib.lib()
 
     def padded(v, fill):
         o = torch.full((m, n_act + pad), fill, device='cuda')

@@ -19,6 +19,7 @@ import torch
 
 import mfg_amd.marl as M
 import mfg_amd.seac as S
+from mfg_amd import learn_lib
 from test_seac import check_loss_and_grads, forward, hyper, load_case, targets
 
 pytestmark = pytest.mark.gpu
@@ -69,7 +70,7 @@ def test_grouped_projection(G, mb):
     roundings (the bias add included), so |out - ref| <= ((1 + u)^(cap + 1) - 1) S <= (cap + 2) u S with u = 2^-24 and
     S = |bias| + sum |v| |w| of the row."""
     g = torch.Generator().manual_seed(100 * G + mb)
-    L = S._seac_lib()
+    L = learn_lib.lib()
     m = G * mb
     pad = 3
     for cap in (1, 32, 70):
@@ -111,7 +112,7 @@ def test_grouped_projection(G, mb):
 
 
 def test_grouped_projection_refuses_bad_sizes():
-    L = S._seac_lib()
+    L = learn_lib.lib()
     z = torch.zeros(1 << 16, device='cuda')
     out = torch.zeros(1 << 10, device='cuda')
     p, o = z.data_ptr(), out.data_ptr()
@@ -138,7 +139,7 @@ def test_grouped_gru_step_is_the_per_block_step(rpg, hd):
     bh = torch.randn((G, 3 * hd), generator=g).cuda()
     h = torch.randn((n, hd), generator=g).cuda()
     keep = (torch.rand(n, generator=g) < 0.7).float().cuda()
-    L = S._seac_lib()
+    L = learn_lib.lib()
 
     def outs():
         return [torch.full((n, hd), -3.0, device='cuda') for _ in range(6)]
@@ -226,10 +227,10 @@ def kernel_head(x, gae, act=None, logits=None, guard=16):
         return torch.full((numel + 2 * guard,), -3.0, device='cuda')
     loss, dl, dc = guarded(A), guarded(lg.numel()), guarded(cr.numel())
     ws = torch.empty(S.seac_ws_bytes(A) // 8, dtype=torch.float64, device='cuda')
-    rc = S._seac_lib().mfg_seac_head(lg.data_ptr(), cr.data_ptr(), A, B, t, x['n_max'], a.data_ptr(), B * A, A, 1,
-                                     rew.data_ptr(), B * A, A, 1, dn.data_ptr(), B, 1, 0, n_act.data_ptr(), HYP[0], gae,
-                                     HYP[2], HYP[1], 1 if x['cross'] else 0, loss[guard:].data_ptr(),
-                                     dl[guard:].data_ptr(), dc[guard:].data_ptr(), ws.data_ptr(), _stream())
+    rc = learn_lib.lib().mfg_seac_head(lg.data_ptr(), cr.data_ptr(), A, B, t, x['n_max'], a.data_ptr(), B * A, A, 1,
+                                       rew.data_ptr(), B * A, A, 1, dn.data_ptr(), B, 1, 0, n_act.data_ptr(), HYP[0],
+                                       gae, HYP[2], HYP[1], 1 if x['cross'] else 0, loss[guard:].data_ptr(),
+                                       dl[guard:].data_ptr(), dc[guard:].data_ptr(), ws.data_ptr(), _stream())
     torch.cuda.synchronize()
     for o in (loss, dl, dc):
         assert bool((o[:guard] == -3.0).all()) and bool((o[-guard:] == -3.0).all()), 'a write outside the outputs'
@@ -312,8 +313,8 @@ def test_seac_head_bad_inputs_give_nan_not_a_fault():
             assert bool((dl[:, 2, 1] == 0).all()) and bool((dc[:, 2, 1] == 0).all())
         rc, loss, dl, dc = kernel_head(x, 0.95)
         assert rc == 0 and bool(torch.isfinite(loss).all())
-    assert S._seac_lib().mfg_seac_head(0, 0, 0, 4, 5, 10, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.99, 0.0, 0.5, 0.01, 0,
-                                       0, 0, 0, 0, _stream()) == -1
+    assert learn_lib.lib().mfg_seac_head(0, 0, 0, 4, 5, 10, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.99, 0.0, 0.5, 0.01,
+                                         0, 0, 0, 0, 0, _stream()) == -1
 
 
 # ---------------------------------------------------------------------------------------------------------------------

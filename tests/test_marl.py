@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from mfg_amd import learn_lib
 from mfg_amd.marl import RecurrentAC, a2c_loss
 
 GOLD = Path(__file__).resolve().parent / 'golden' / 'marl_a2c.npz'
@@ -453,13 +454,13 @@ def test_packed_grads_match_dense(m, cap, k, e):
     iu, vc = idx.to(torch.uint16).cuda(), val.cuda()
     if k <= M._DENSIFY_MAX_K:
         dd = torch.full((m, k + 3), -1.0, device='cuda')  # row stride k + 3: the pad columns stay untouched
-        assert M._gru_lib().mfg_packed_densify(iu.data_ptr(), vc.data_ptr(), m, cap, k, dd.data_ptr(), k + 3,
-                                               torch.cuda.current_stream().cuda_stream) == 0
+        assert learn_lib.lib().mfg_packed_densify(iu.data_ptr(), vc.data_ptr(), m, cap, k, dd.data_ptr(), k + 3,
+                                                  torch.cuda.current_stream().cuda_stream) == 0
         assert torch.equal(dd[:, :k].cpu(), d.float()) and bool((dd[:, k:] == -1).all())
     else:  # past the kernel's bound: refused, and _packed_grads takes the scatter_add rows instead
         dd = torch.empty((m, k), device='cuda')
-        assert M._gru_lib().mfg_packed_densify(iu.data_ptr(), vc.data_ptr(), m, cap, k, dd.data_ptr(), k,
-                                               torch.cuda.current_stream().cuda_stream) == -1
+        assert learn_lib.lib().mfg_packed_densify(iu.data_ptr(), vc.data_ptr(), m, cap, k, dd.data_ptr(), k,
+                                                  torch.cuda.current_stream().cuda_stream) == -1
     ref_w, ref_b = (d.t() @ g.double()).t(), g.double().sum(0)
     gw, gb = M._packed_grads(iu, vc, g.cuda(), k)
     assert gw.shape == (e, k) and gb.shape == (e,)
@@ -479,7 +480,7 @@ def test_packed_project_kernel_matches_dense():
     d.scatter_add_(1, idx, val.double())
     ref = d @ w.double().t() + b.double()
     out = torch.empty((m, e), device='cuda')
-    L = M._gru_lib()
+    L = learn_lib.lib()
     iu, vc, wt, bc = idx.to(torch.uint16).cuda(), val.cuda(), w.t().contiguous().cuda(), b.cuda()
     assert L.mfg_packed_project(iu.data_ptr(), vc.data_ptr(), m, cap, wt.data_ptr(), bc.data_ptr(), e, k,
                                 out.data_ptr(), e, torch.cuda.current_stream().cuda_stream) == 0
@@ -491,7 +492,7 @@ def test_sample_categorical_kernel_distribution():
     """mfg_sample_categorical: inversion sampling at caller-drawn uniforms; exact picks at chosen uniforms and the
     empirical frequencies of 2M draws within 0.003 of softmax(logits)."""
     import mfg_amd.marl as M
-    L = M._gru_lib()
+    L = learn_lib.lib()
     st = torch.cuda.current_stream().cuda_stream
     logits = torch.tensor([0.5, -1.0, 2.0, 0.0, 1.0], device='cuda')
     p = torch.softmax(logits.double(), 0).cpu()

@@ -75,6 +75,39 @@ def test_hip_library_exports_every_declared_symbol():
     assert lib.mfg_abi_version() == 5
 
 
+def test_learn_lib_argtypes_match_the_header():
+    """mfg_amd/learn_lib.py's one table against every prototype of include/mfg_learn.h: the same functions in the
+    same order, the same number of parameters, and per parameter pointer -> c_void_p, int64_t -> c_int64,
+    int -> c_int, float -> c_float (an int for an int64_t stride is silent until a large batch); the structure's
+    fields against the typedef's. No GPU and no library: the table is data."""
+    from mfg_amd import learn_lib
+    txt = re.sub(r'/\*.*?\*/', '', (ROOT / 'include' / 'mfg_learn.h').read_text(), flags=re.S)
+    protos = re.findall(r'\b(\w+)\s+(mfg_\w+)\s*\(([^)]*)\)\s*;', txt)
+    scalar = {'int64_t': C.c_int64, 'int': C.c_int, 'float': C.c_float}
+    want = {}
+    for ret, name, params in protos:
+        assert ret == 'int', f'{name} returns {ret}: learn_lib binds every restype as c_int'
+        args = []
+        for p in params.split(','):
+            if '*' in p:
+                args.append(C.c_void_p)
+            else:
+                ctype = ' '.join(w for w in p.split()[:-1] if w != 'const')  # the last word is the name
+                assert ctype in scalar, f'{name}: parameter "{p.strip()}" has a type the table cannot express'
+                args.append(scalar[ctype])
+        want[name] = args
+    assert len(want) == 12 and 'mfg_policy_act' in want and 'mfg_gru_fwd_step' in want
+    assert list(learn_lib.ARGTYPES) == list(want)
+    for name, args in want.items():
+        got = learn_lib.ARGTYPES[name]
+        assert len(got) == len(args), f'{name}: {len(got)} argtypes for {len(args)} parameters'
+        for k, (g, a) in enumerate(zip(got, args)):
+            assert g is a, f'{name}: parameter {k} is bound as {g.__name__}, the header says {a.__name__}'
+    fields = re.search(r'typedef struct mfg_actor_weights \{(.*?)\}', txt, flags=re.S).group(1)
+    assert [f for f, _ in learn_lib.ActorWeights._fields_] == re.findall(r'\*(\w+)', fields)
+    assert all(t is C.c_void_p for _, t in learn_lib.ActorWeights._fields_)
+
+
 def _hip_lib():
     from mfg_amd.engine import LIB_PATH
     if not LIB_PATH.exists():
