@@ -288,6 +288,8 @@ typedef struct mfg_variant {
                                  strides over several envs */
   int32_t serial;             /* 1: every kernel on the caller's stream in launch order (no resets or replay on the
                                  engine's second stream beside the render): per-kernel times for attribution */
+  int32_t obs_generic;        /* 1: dense obs of pomdp_r 1..3 through the generic render (window geometry read from the
+                                 spec at run time) instead of the one compiled for that radius: parity and A/B runs */
 } mfg_variant;
 int mfg_create_variant(const mfg_spec* spec, int device, int64_t n_envs, const mfg_variant* variant,
                        mfg_engine** out);

@@ -33,6 +33,7 @@ struct mfg_engine {
   bool replay_each = false; // pay the shuffle debt after every step, not once per call (long resets + in-step RNG)
   int obs_nwv = 1;          // waves per env of the render (> 1: multi-wave render, k_obs_mw)
   bool replay2 = false;     // two-wave replay (k_replay2) for floor lists whose 1-wave slice fills a SIMD
+  int obs_geo_r = 0;        // > 0: dense obs through the render with this pomdp_r's window geometry folded (ObsGeo)
   struct Mark { int k; hipEvent_t a, b; };
   std::vector<Mark> marks;
   std::string err;  // mfg_last_error(e)
@@ -331,7 +332,7 @@ extern "C" int mfg_create_variant(const mfg_spec* s, int device, int64_t n_envs,
   if (!s || !out) return fail("null argument");
   if (n_envs < 1) return fail("n_envs must be >= 1");
   if (validate_spec(s)) return -1;
-  const mfg_variant none{0, 0, 0, 0, 0, 0};
+  const mfg_variant none{0, 0, 0, 0, 0, 0, 0};
   DevGuard g(device);
   return create_impl(s, device, n_envs, v ? *v : none, out);
 }
@@ -721,6 +722,16 @@ static int create_impl(const mfg_spec* s, int device, int64_t n_envs, const mfg_
     delete e; return fail("spec upload failed");
   }
   e->maxpts = h.maxpts;
+  // dense obs of pomdp_r 1..3 through the render compiled for that radius (launch_obs_geo): only when every value it
+  // folds is what this spec says, and the render is the single-wave one (mfg_variant.obs_generic: never)
+  e->obs_geo_r = 0;
+  if (!v.obs_generic && h.r >= 1 && h.r <= 3) {
+    const int R = h.r, d = 2 * R + 1, fw = 2 * d + 1;
+    static const int NRAYS[] = {24, 38, 44};  // ObsGeo<R>::nrays
+    if (h.oh == d && h.ow == d && h.dd == d * d && h.fr == d && h.fv_words == align_up(fw * fw, 4) &&
+        h.maxpts == 2 * R + 2 && h.nrays == NRAYS[R - 1] && h.A <= MFG_WAVE)
+      e->obs_geo_r = R;
+  }
   {  // k_resetdone's grid: the waves resident at once (one round; each strides over the done list)
     const int wpb = wpb_for(h.lds_full);
     int per_cu = 0, n_cu = 0;
@@ -806,7 +817,8 @@ extern "C" int mfg_destroy(mfg_engine* e) {
 
 // record layout for host-side decoding (tests, snapshots):
 // [size, o_hdr, ..., o_perm, lmax, obs_agent_stride, lds_full, xchg_ordered, o_machines, ..., scratch_bytes, o_logic,
-//  reset_overlap (1: with auto-reset and obs, a step's resets and their render run on the engine's second stream)]
+//  reset_overlap (1: with auto-reset and obs, a step's resets and their render run on the engine's second stream),
+//  obs_geo_r (> 0: dense obs are rendered by the kernels with this pomdp_r's window geometry folded, 0: the generic ones)]
 extern "C" int mfg_layout(const mfg_engine* e, int32_t* out) {
   const MfgLayout& L = e->h.L;
   const int32_t v[] = {L.size, L.o_hdr, L.o_rule_ctr, L.o_agent_pos, L.o_agent_arr, L.o_agent_par, L.o_frozen_org,
@@ -815,7 +827,7 @@ extern "C" int mfg_layout(const mfg_engine* e, int32_t* out) {
                        e->h.lmax, e->h.obs_agent_stride, e->h.lds_full, e->h.xchg_ordered, L.o_machines,
                        L.o_maints, L.o_mstate, L.o_mpath, L.o_grank, e->h.dirt_cap, e->h.lds_logic, e->h.lds_obs,
                        e->h.lds_replay_per_wave, e->h.bfs_off, e->h.bfs_bytes, e->h.max_pairs, e->h.scratch_bytes,
-                       L.o_logic, e->overlap ? 1 : 0};
+                       L.o_logic, e->overlap ? 1 : 0, e->obs_geo_r};
   const int n = (int)(sizeof(v) / sizeof(v[0]));
   for (int i = 0; i < n; i++) out[i] = v[i];
   return n;
@@ -860,6 +872,10 @@ static hipError_t launch_obs_t(mfg_engine* e, OT* obs, const ObsPacked& pk, hipS
   L.d_state = e->d_state;
   L.mm = e->h.mmax || e->h.kmax;
   L.dirt = e->h.dirt_cap != 0;
+  if constexpr (PK == 0 && (MP == 4 || MP == 6 || MP == 8)) {
+    constexpr int R = MP / 2 - 1;
+    if (e->obs_geo_r == R && !L.mw) return launch_obs_geo<R, OT>(L, obs, st, skip, list);
+  }
   return launch_obs_inst<MP, OT, PK>(L, obs, pk, st, skip, list);
 }
 

@@ -2421,8 +2421,10 @@ struct RayLane {
   __device__ __forceinline__ int dx(int p) const { return (int)(int8_t)((pk[p >> 1] >> ((p & 1) * 16)) & 0xFF); }
   __device__ __forceinline__ int dy(int p) const { return (int)(int8_t)((pk[p >> 1] >> ((p & 1) * 16 + 8)) & 0xFF); }
   static_assert(MAXPTS % 2 == 0 && NW * 4 == 2 * MAXPTS, "a ray's points are whole dwords");
-  __device__ __forceinline__ void load(SpecP S, int ray) {
-    const bool has = ray < S->nrays;
+  __device__ __forceinline__ void load(SpecP S, int ray) { load(S, ray, S->nrays); }
+  // (nrays: the spec's ray count, where the caller has it as a constant)
+  __device__ __forceinline__ void load(SpecP S, int ray, int nrays) {
+    const bool has = ray < nrays;
     // dword loads: a ray's 2 * MAXPTS bytes start on a 4-B boundary (MAXPTS is even, the table is a device
     // allocation)
     const uint32_t* pts = (const uint32_t*)S->ray_pts + (size_t)(has ? ray : 0) * NW;
@@ -2635,17 +2637,35 @@ __device__ __forceinline__ void tbl_sync() {
     wave_sync();
   }
 }
-template <int MAXPTS, typename OT, bool MM, int PK, bool DIRT, bool MW>
+// R > 0 (GEO): the window geometry of pomdp_r == R is compile-time (single-wave dense render of the square
+// (2R + 1)^2 window: oh, ow, dd, fr, fw, the first-visit table size, the ray count and the point stride, so the table
+// bases, the reciprocals and the loop bounds cost no SGPRs across the agent loop). mfg_create selects it only after
+// checking each folded value against the spec (obs_geo_r); R == 0 reads them from the spec.
+template <int R>
+struct ObsGeo {
+  static constexpr int oh = 2 * R + 1, dd = oh * oh, fr = oh, fw = 2 * fr + 1, fv_words = (fw * fw + 3) & ~3;
+  static constexpr int maxpts = 2 * R + 2;                       // points per ray: fr + 1, the MAXPTS bucket
+  static constexpr int nrays = R == 1 ? 24 : (R == 2 ? 38 : 44);  // unique ray targets of radius 2R + 1 (R <= 3)
+};
+template <int MAXPTS, typename OT, bool MM, int PK, bool DIRT, bool MW, int R = 0>
 __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPacked& pk, int wv, int nwv,
                           int slot = 0) {
   SpecP S = e.S;
   constexpr bool LR = MAXPTS == 0;
+  constexpr bool GEO = R > 0;
+  static_assert(!GEO || (R <= 3 && MAXPTS == ObsGeo<R>::maxpts && PK == 0 && !MW), "folded window geometry");
+  typedef ObsGeo<GEO ? R : 1> G;
   constexpr int RMP = LR ? 2 : MAXPTS;  // RayLane width (unused by the long-ray walk)
   typedef obs_u32<LR> tu32;
   // window: oh x ow cells from (wx0, wy0) = agent - r, or the whole level at (0, 0) when pomdp_r == 0
   // (observation_builder.py:152-158); rays and the first-visit table have radius fr (Q13)
-  const int A = S->A, H = S->s.H, W = S->s.W, oh = S->oh, ow = S->ow, dd = S->dd, fr = S->fr;
-  const bool full = S->r == 0;
+  const int A = S->A, H = S->s.H, W = S->s.W, oh = GEO ? G::oh : S->oh, ow = GEO ? G::oh : S->ow,
+            dd = GEO ? G::dd : S->dd, fr = GEO ? G::fr : S->fr;
+  // (read where they are used, as the run-time values always were)
+#define OBS_GEO_OR(CONST, SPEC) (GEO ? (CONST) : (SPEC))
+#define OBS_NRAYS OBS_GEO_OR(G::nrays, S->nrays)
+#define OBS_FV_WORDS OBS_GEO_OR(G::fv_words, S->fv_words)
+  const bool full = !GEO && S->r == 0;
   const float invw = 1.0f / (float)ow;
   const int lane = e.lane;
   const bool frozen = e.H(H_FROZEN) != 0;
@@ -2673,7 +2693,7 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
   uint32_t* fv = LR ? (uint32_t*)(S->obs_pool + (size_t)slot * (size_t)S->obs_slot_bytes)
                     : (uint32_t*)(e.scratch + 3 * S->pairs_lds + (MW ? wv * (S->lds_obs_wave >> 2) : 0));
   const int fw = 2 * fr + 1;
-  uint8_t* wsup = (uint8_t*)(fv + S->fv_words);  // [dd] window cells whose wall or door the dedupe suppressed
+  uint8_t* wsup = (uint8_t*)(fv + OBS_FV_WORDS);  // [dd] window cells whose wall or door the dedupe suppressed
   const int nsup4 = (dd + 3) >> 2;
   // dirt suppression bitmap for groups wider than a wave: after the per-lane sink words of the ray walk
   tu32* dsup = (tu32*)((uint32_t*)(wsup + ((dd + 15) & ~15)) + MFG_WAVE);
@@ -2708,7 +2728,7 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
   const int agp = lane < A ? e.agpos()[lane] : -1;
   const int org_l = lane < A ? (frozen ? e.forg()[lane] : agp) : -1;
   const int nT = e.H(H_N_DIRT);
-  const int npass = (S->nrays + MFG_WAVE - 1) / MFG_WAVE;
+  const int npass = (OBS_NRAYS + MFG_WAVE - 1) / MFG_WAVE;
   const int pA0 = lane < npairs ? pairs.get(lane, 0) : 0, pB0 = lane < npairs ? pairs.get(lane, 1) : 0;
   // agent and ray-origin coordinates: one vector division per render, read per agent with v_readlane
   const int agx = agp / W, agy = agp % W, orgx = org_l / W, orgy = org_l % W;
@@ -2717,7 +2737,7 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
   constexpr bool HOIST_RAYS = !LR && MAXPTS <= 8 && PK == 0;  // (packed renders: per agent, measured faster)
   constexpr bool PREFETCH_RS = !LR && MAXPTS <= 8 && PK != 2;
   RayLane<RMP> ray0;
-  if constexpr (HOIST_RAYS) ray0.load(S, lane);
+  if constexpr (HOIST_RAYS) ray0.load(S, lane, OBS_NRAYS);
   // ... and their static light-blocking words are fetched one agent ahead (an L2 round trip behind a
   // dependent cell_f load, hidden under the previous agent's dedupe and placement)
   int pf_ofl = -1;
@@ -2726,15 +2746,26 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
     const int og = (!LR || ag < MFG_WAVE) ? rl(orgx, ag) * W + rl(orgy, ag) : uni(frozen ? e.forg()[ag] : e.agpos()[ag]);
     pf_ofl = S->ray_static ? uni((int)S->cell_f[og]) : -1;
     if (pf_ofl >= 0) {
-      const bool has = lane < S->nrays;
-      const uint32_t* rs = S->ray_static + ((size_t)pf_ofl * S->nrays + (has ? lane : 0)) * 3;
+      const bool has = lane < OBS_NRAYS;
+      const uint32_t* rs = S->ray_static + ((size_t)pf_ofl * OBS_NRAYS + (has ? lane : 0)) * 3;
       pf_b = has ? rs[0] : 0u;
       pf_c = has ? rs[1] : 0u;
       pf_d = has ? rs[2] : 0u;
     }
   };
   if constexpr (PREFETCH_RS) rs_fetch(MW ? wv : 0);
+  const int lane_outer = lane;
   for (int a = MW ? wv : 0; a < A; a += MW ? nwv : 1) {
+#ifndef MFG_OBS_GEO_LANE_OPAQUE
+#define MFG_OBS_GEO_LANE_OPAQUE 1
+#endif
+    // GEO: with the loop bounds and table offsets constant, everything derived from the lane index alone (window cell,
+    // its row and column, a table address per element size) is agent independent and gets hoisted out of this loop
+    // into registers held across it: C3 f64 71 VGPRs, 7 waves per SIMD and 4 VGPRs in scratch. An opaque per-agent
+    // copy of the lane index keeps those few VALU ops inside the loop, where the generic render has them: 55 VGPRs,
+    // 8 waves, no scratch.
+    int lane = lane_outer;
+    if constexpr (GEO && MFG_OBS_GEO_LANE_OPAQUE) asm volatile("" : "+v"(lane));
     int apos, ax, ay, ox, oy;
     if (!LR || a < MFG_WAVE) {
       apos = rl(agp, a);
@@ -2746,10 +2777,10 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
       ax = apos / W; ay = apos - ax * W;
       ox = og / W; oy = og - ox * W;
     }
-    const int wx0 = full ? 0 : ax - S->r, wy0 = full ? 0 : ay - S->r;
+    const int wx0 = full ? 0 : ax - OBS_GEO_OR(R, S->r), wy0 = full ? 0 : ay - OBS_GEO_OR(R, S->r);
     // origin floor index (static table)
     const int ofl = PREFETCH_RS ? pf_ofl : (S->ray_static ? uni((int)S->cell_f[ox * W + oy]) : -1);
-    for (int i = lane; i < S->fv_words; i += MFG_WAVE) fv[i] = 0xFFFFFFFFu;
+    for (int i = lane; i < OBS_FV_WORDS; i += MFG_WAVE) fv[i] = 0xFFFFFFFFu;
     for (int i = lane; i < nsup4; i += MFG_WAVE) ((uint32_t*)wsup)[i] = 0u;
     for (int i = lane; i < ndsup; i += MFG_WAVE) dsup[i] = 0u;
     for (int i = lane; i < (wide ? 4 : 2) * dd; i += MFG_WAVE) amw[i] = 0u;
@@ -2817,8 +2848,14 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
     for (int pass = 0; pass < npass; pass++) {
       const int ray_id = pass * MFG_WAVE + lane;
       RayLane<RMP> ray;
-      if (HOIST_RAYS && pass == 0) ray = ray0;
-      else ray.load(S, ray_id);
+      if constexpr (GEO) {
+        // one pass. Only the length and the diagonal mask stay in registers across the agent loop: the first-visit
+        // slots of the points are agent independent (hoisted from the walk below), and the point offsets themselves
+        // are read again where a spec has no static table
+        ray.len = ray0.len;
+        ray.diag = ray0.diag;
+      } else if (HOIST_RAYS && pass == 0) ray = ray0;
+      else ray.load(S, ray_id, OBS_NRAYS);
       // branch-free: every point tests its cell and (from p = 1) both corner cells; the static diagonal
       // mask keeps the corner test only on diagonal steps: cut when both orthogonal neighbours block
       // light (ray_caster.py:89-96)
@@ -2835,8 +2872,8 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
           dyn = pf_d;
           if (a + (MW ? nwv : 1) < A) rs_fetch(a + (MW ? nwv : 1));
         } else {
-          const bool has = ray_id < S->nrays;
-          const uint32_t* rs = S->ray_static + ((size_t)ofl * S->nrays + (has ? ray_id : 0)) * 3;
+          const bool has = ray_id < OBS_NRAYS;
+          const uint32_t* rs = S->ray_static + ((size_t)ofl * OBS_NRAYS + (has ? ray_id : 0)) * 3;
           blkm = has ? rs[0] : 0u;
           cutm = has ? rs[1] : 0u;
           dyn = has ? rs[2] : 0u;
@@ -2844,7 +2881,7 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
         while (dyn) {
           const int p = __ffs((int)dyn) - 1;
           dyn &= dyn - 1;
-          const int8_t* pt = S->ray_pts + ((size_t)ray_id * S->maxpts + p) * 2;
+          const int8_t* pt = S->ray_pts + ((size_t)ray_id * OBS_GEO_OR(G::maxpts, S->maxpts) + p) * 2;
           const int x = ox + pt[0], y = oy + pt[1];
           blkm |= light_block_bf<MM>(e, x, y) ? ((PM)1 << p) : (PM)0;
           if (p > 0 && ((ray.diag >> p) & 1u)) {
@@ -2853,6 +2890,7 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
           }
         }
       } else {
+        if constexpr (GEO) ray.load(S, ray_id, OBS_NRAYS);
 #pragma unroll
         for (int p = 0; p < RMP; p++) {
           const int x = ox + ray.dx(p), y = oy + ray.dy(p);
@@ -2876,7 +2914,7 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
       // ray 0's rank 0, stored once below instead of a 64-lane same-address atomic
 #pragma unroll
       for (int p = 1; p < RMP; p++)
-        atomicMin(((vism >> p) & 1u) ? &fv[(ray.dx(p) + fr) * fw + ray.dy(p) + fr] : sink,
+        atomicMin(((vism >> p) & 1u) ? &fv[((GEO ? ray0 : ray).dx(p) + fr) * fw + (GEO ? ray0 : ray).dy(p) + fr] : sink,
                   (uint32_t)((ray_id << RayLane<RMP>::RSH) + p));
     }
     if (lane == 0) fv[fr * fw + fr] = 0u;
@@ -3162,8 +3200,19 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
       tbl_sync<LR>();
       const int ne = nl * dd;
       const float invdd = 1.0f / (float)dd;
-      for (int e0 = 0; e0 < ne; e0 += MFG_WAVE) {
-        const int el = min(e0 + lane, ne - 1);
+      // GEO: the runs start on a line boundary of the obs buffer, not at the agent's block (343 values at C3: no
+      // multiple of a line), so a 64-lane store covers whole lines and only the block's two ends are partial. The
+      // first run's lanes before the block repeat its first value, as the last run's repeat the last. At C3 the
+      // shift fits the last run's slack (343 + 15 <= 384: still six runs). MFG_OBS_GEO_ALIGN: the boundary in bytes
+      // (0: runs from the block's start, as in the generic render)
+#ifndef MFG_OBS_GEO_ALIGN
+#define MFG_OBS_GEO_ALIGN 128
+#endif
+      int e_first = 0;
+      if constexpr (GEO && MFG_OBS_GEO_ALIGN > 0)
+        e_first = -(int)(((size_t)out_a / sizeof(OT)) & (MFG_OBS_GEO_ALIGN / sizeof(OT) - 1));
+      for (int e0 = e_first; e0 < ne; e0 += MFG_WAVE) {
+        const int el = min((GEO && MFG_OBS_GEO_ALIGN > 0) ? max(e0 + lane, 0) : e0 + lane, ne - 1);
         const int l = (int)(((float)el + 0.5f) * invdd), c = el - l * dd;
         const uint32_t ct = ctag[c];
         const u64 am = (u64)amw[2 * c] | ((u64)amw[2 * c + 1] << 32);
@@ -3259,6 +3308,9 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
       }
     }
   }
+#undef OBS_NRAYS
+#undef OBS_FV_WORDS
+#undef OBS_GEO_OR
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3655,7 +3707,7 @@ k_resetdone(const MfgDevSpec* S_, uint8_t* state, long long B, int rd_slot) {
 // Observation render of every env into obs[env] (read-only on the state). MM: the spec has machines or
 // maintainers (their tags, identifiers and dedupe); compiled out otherwise to keep the VGPR budget.
 // One env's render (observation_builder.py:138-235) in its LDS slice.
-template <int MAXPTS, typename OT, bool MM, int PK, bool DIRT, bool MW = false>
+template <int MAXPTS, typename OT, bool MM, int PK, bool DIRT, bool MW = false, int R = 0>
 __device__ __forceinline__ void obs_env(SpecP S, uint8_t* slice, const uint8_t* state, long long env, OT* obs,
                                         ObsPacked pk, int wv = 0, int nwv = 1, int slot = 0) {
   // slice: [lean record][cell map][pairs] (+ per-wave tables, build_obs)
@@ -3680,9 +3732,9 @@ __device__ __forceinline__ void obs_env(SpecP S, uint8_t* slice, const uint8_t* 
     pk.val = pk.val ? pk.val + ea * pk.cap : nullptr;
     pk.cnt = pk.cnt ? pk.cnt + ea : nullptr;
     pk.emb = pk.emb ? pk.emb + ea * pk.E : nullptr;
-    build_obs<MAXPTS, OT, MM, PK, DIRT, MW>(e, nullptr, pg, pk, wv, nwv, slot);
+    build_obs<MAXPTS, OT, MM, PK, DIRT, MW, R>(e, nullptr, pg, pk, wv, nwv, slot);
   } else {
-    build_obs<MAXPTS, OT, MM, PK, DIRT, MW>(e, obs + (size_t)env * S->A * S->obs_agent_stride, pg, pk, wv, nwv, slot);
+    build_obs<MAXPTS, OT, MM, PK, DIRT, MW, R>(e, obs + (size_t)env * S->A * S->obs_agent_stride, pg, pk, wv, nwv, slot);
   }
   // k_obs reads only [0, o_mt) of the record and stores only this word: the replay of the same call may run beside it
   // on the engine's second stream and writes H_DEBT / H_MT_IDX (single words) and [o_mt, o_perm + 2 nf) (replay_env)
@@ -3694,8 +3746,12 @@ __device__ __forceinline__ void obs_env(SpecP S, uint8_t* slice, const uint8_t* 
 // Render of every env (skip: envs k_logic put on this step's done list, rendered by k_obs_list after their reset
 // on the engine's second stream; null = none). With auto-reset, mfg_step renders the envs that did not finish
 // on the caller's stream while the finished ones are reset and rendered beside it.
-template <int MAXPTS, typename OT, bool MM, int PK, bool DIRT>
-static __global__ void __launch_bounds__(MFG_WPB * 64) __attribute__((amdgpu_waves_per_eu(MAXPTS <= 8 ? 7 : 1))) k_obs(const MfgDevSpec* S_, const uint8_t* state, long long B,
+// R > 0: the render with pomdp_r == R's window geometry folded (build_obs, ObsGeo)
+#ifndef MFG_OBS_GEO_WPE
+#define MFG_OBS_GEO_WPE 7  // waves per SIMD asked for the folded-geometry render
+#endif
+template <int MAXPTS, typename OT, bool MM, int PK, bool DIRT, int R = 0>
+static __global__ void __launch_bounds__(MFG_WPB * 64) __attribute__((amdgpu_waves_per_eu(R > 0 ? MFG_OBS_GEO_WPE : (MAXPTS <= 8 ? 7 : 1)))) k_obs(const MfgDevSpec* S_, const uint8_t* state, long long B,
                                                       OT* obs, ObsPacked pk, const uint8_t* skip) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   SpecP S = (SpecP)S_;
@@ -3703,7 +3759,7 @@ static __global__ void __launch_bounds__(MFG_WPB * 64) __attribute__((amdgpu_wav
   const long long env = (long long)blockIdx.x * (blockDim.x >> 6) + wid;
   if (env >= B) return;
   if (skip && skip[env]) return;
-  obs_env<MAXPTS, OT, MM, PK, DIRT>(S, smem + (size_t)wid * S->lds_obs, state, env, obs, pk);
+  obs_env<MAXPTS, OT, MM, PK, DIRT, false, R>(S, smem + (size_t)wid * S->lds_obs, state, env, obs, pk);
 }
 // Multi-wave render: one env per workgroup of nwv waves (specs whose per-env render slice is large, C5: a
 // 128 x 128 u16 cell map; the waves share it and split the agents)
@@ -3750,7 +3806,7 @@ static __global__ void __launch_bounds__(MFG_WAVE) k_obs_lr(const MfgDevSpec* S_
   }
 }
 // Render of the envs of a done list (rd_list row: [0] = count, [2..] = envs): a resident grid strides over it.
-template <int MAXPTS, typename OT, bool MM, int PK, bool DIRT>
+template <int MAXPTS, typename OT, bool MM, int PK, bool DIRT, int R = 0>
 static __global__ void __launch_bounds__(MFG_WPB * 64) k_obs_list(const MfgDevSpec* S_, const uint8_t* state, long long B,
                                                            OT* obs, ObsPacked pk, const int32_t* list) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -3760,7 +3816,8 @@ static __global__ void __launch_bounds__(MFG_WPB * 64) k_obs_list(const MfgDevSp
   const long long nw = (long long)gridDim.x * (blockDim.x >> 6);
   for (long long q = (long long)blockIdx.x * (blockDim.x >> 6) + wid; q < n; q += nw) {
     const long long env = uni(list[2 + q]);
-    if (env >= 0 && env < B) obs_env<MAXPTS, OT, MM, PK, DIRT>(S, smem + (size_t)wid * S->lds_obs, state, env, obs, pk);
+    if (env >= 0 && env < B)
+      obs_env<MAXPTS, OT, MM, PK, DIRT, false, R>(S, smem + (size_t)wid * S->lds_obs, state, env, obs, pk);
   }
 }
 
@@ -4070,6 +4127,32 @@ hipError_t launch_obs_inst(const ObsLaunch& L, OT* obs, const ObsPacked& pk, hip
                            L.d_state, L.B, obs, pk, skip);                                                       \
     }                                                                                                            \
   }
+// the single-wave dense render with pomdp_r == R's window geometry folded (k_obs / k_obs_list <2R + 2, OT, MM, 0, DIRT,
+// R>; instantiated in mfg_obs_g.hip). mfg_create decides whether a spec takes it (mfg_engine.obs_geo_r).
+template <int R, typename OT>
+hipError_t launch_obs_geo(const ObsLaunch& L, OT* obs, hipStream_t st, const uint8_t* skip, const int32_t* list);
+#define MFG_OBS_GEO_LAUNCH_IF(MMV, DV)                                                                           \
+  if (L.mm == MMV && L.dirt == DV) {                                                                             \
+    if (list)                                                                                                    \
+      hipLaunchKernelGGL((k_obs_list<2 * R + 2, OT, MMV, 0, DV, R>), dim3(L.grid), dim3(L.W * 64), L.lds, st,    \
+                         L.d_spec, L.d_state, L.B, obs, ObsPacked{}, list);                                      \
+    else                                                                                                         \
+      hipLaunchKernelGGL((k_obs<2 * R + 2, OT, MMV, 0, DV, R>), dim3(L.grid), dim3(L.W * 64), L.lds, st,         \
+                         L.d_spec, L.d_state, L.B, obs, ObsPacked{}, skip);                                      \
+  }
+#define MFG_DEFINE_LAUNCH_OBS_GEO                                                                                \
+  template <int R, typename OT>                                                                                  \
+  hipError_t launch_obs_geo(const ObsLaunch& L, OT* obs, hipStream_t st, const uint8_t* skip,                    \
+                            const int32_t* list) {                                                               \
+    MFG_OBS_GEO_LAUNCH_IF(true, true) else MFG_OBS_GEO_LAUNCH_IF(true, false)                                    \
+    else MFG_OBS_GEO_LAUNCH_IF(false, true) else MFG_OBS_GEO_LAUNCH_IF(false, false)                             \
+    return hipGetLastError();                                                                                    \
+  }
+#define MFG_INSTANTIATE_OBS_GEO(R)                                                                               \
+  template hipError_t launch_obs_geo<R, double>(const ObsLaunch&, double*, hipStream_t, const uint8_t*,          \
+                                                const int32_t*);                                                 \
+  template hipError_t launch_obs_geo<R, float>(const ObsLaunch&, float*, hipStream_t, const uint8_t*,            \
+                                               const int32_t*);
 // explicit instantiations of one ray length (the obs modes: packed + fused projection, packed entries only, f64, f32)
 #define MFG_INSTANTIATE_OBS(MP)                                                                                  \
   template hipError_t launch_obs_inst<MP, float, 2>(const ObsLaunch&, float*, const ObsPacked&, hipStream_t,      \
