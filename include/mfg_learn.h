@@ -34,13 +34,23 @@ int mfg_packed_densify(const uint16_t* idx, const float* val, int64_t m, int cap
                        void* stream);
 
 /* out[r][:e_dim] = bias + sum_j val[r][j] wt[idx[r][j]] for the packed rows (wt [k][e_dim] = obs_proj.weight^T), the
- * projection the render fuses (mfg_packed_obs.emb), for rows held outside a render (the learner's window slide). */
+ * projection the render fuses (mfg_packed_obs.emb), for rows held outside a render (the learner's window slide).
+ * Rows front-compacted as the engine writes them (include/mfg.h: the nonzero entries first, slots >= count idx 0 /
+ * val 0): the kernel stops after the first 64-entry chunk that is not all nonzero, so entries behind a zero value in
+ * an earlier chunk are outside its contract (mfg_packed_project_grouped visits every entry). Entries with idx >= k are
+ * skipped; the products are added in entry order, then the bias: a row without entries gives the bias exactly, and on
+ * such rows the result equals mfg_packed_project_grouped's with g = 1, all = 0 bit for bit. Any e_dim >= 1; columns
+ * past e_dim of a row (out_row > e_dim) are untouched. */
 int mfg_packed_project(const uint16_t* idx, const float* val, int64_t m, int cap, const float* wt, const float* bias,
                        int e_dim, int k, float* out, int64_t out_row, void* stream);
 
 /* out[r] ~ Categorical(logits = logits[r][:n_act]) by inversion at u[r] in [0, 1) (the acting step's
- * Categorical(logits).sample(), base_ac.py:74-76, with the uniforms drawn by the caller); -1 for a row whose
- * logits are not finite (torch.distributions would raise there) */
+ * Categorical(logits).sample(), base_ac.py:74-76, with the uniforms drawn by the caller): the first action a with
+ * u s < sum_{j <= a} expf(l_j - max) in f32, s the whole sum, the last action when rounding passes the last bin.
+ * Columns past n_act of a row (logit_row > n_act) are not read. A common offset of the row changes nothing. An action
+ * of probability 0 in f32 (a logit ~104 or more below the maximum, or -inf beside finite ones, which
+ * torch.distributions.Categorical accepts as well) is never picked, at u = 0 and u = 1 - 2^-24 included. -1 for a row
+ * that is no distribution: every logit -inf, any +inf or any NaN (torch.distributions would raise there). */
 int mfg_sample_categorical(const float* logits, int64_t logit_row, int n_act, const float* u, int64_t n, int32_t* out,
                            void* stream);
 
@@ -143,7 +153,9 @@ typedef struct mfg_actor_weights {
  *   lg = Wb tanh(Wa h' + ba) + bb                                                    -> logits_out (may be NULL)
  *   act = greedy ? argmax(lg[:n_act[net]]) (lowest index on ties)
  *                : mfg_sample_categorical's inversion at u[b][i] over lg[:n_act[net]];
- *         -1 for non-finite logits or n_act[net] outside [1, n_max]                  -> act_out
+ *         -1 for n_act[net] outside [1, n_max] or a row that is no distribution: every logit -inf, any +inf or any
+ *         NaN among lg[:n_act[net]] (a -inf logit beside finite ones is an action of probability 0, never sampled,
+ *         as in mfg_sample_categorical; greedy never picks it either)                -> act_out
  * emb and h are read at b * *_env + i * *_agent (elements): engine order [B][A][..] and agent-major [A][B][..] both
  * work in place. prev_action / act_out i32, u f32 and logits_out [..][n_max] (all n_max columns are written) are
  * [n_envs][n_agents] in engine order; prev_done u8 [n_envs]; n_act i32 [g] (device). u may be NULL with greedy.

@@ -20,12 +20,31 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {
 }
 
 // mx = max_j l[j] and s = sum_j expf(l[j] - mx) over a row of n logits. fmaxf drops a NaN operand, the sum keeps it:
-// s is finite and positive (and mx finite) exactly when every logit is finite. Callers test what they need of that.
+// s is finite and positive exactly when the row is a distribution: no NaN, no +inf, and not -inf throughout (a -inf
+// logit beside finite ones adds expf(-inf) = 0, an action of probability 0). The sampling callers test that.
 __device__ __forceinline__ void row_max_expsum(const float* __restrict__ l, int n, float& mx, float& s) {
   mx = l[0];
   for (int j = 1; j < n; j++) mx = fmaxf(mx, l[j]);
   s = 0.0f;
   for (int j = 0; j < n; j++) s += expf(l[j] - mx);
+}
+
+// The loss heads' view of a row: lse = log sum_j exp(l[j]) as mx + logf(s), and true exactly when every logit is
+// finite. A -inf logit that is not the maximum leaves mx and s finite (row_max_expsum), but its entropy term
+// expf(-inf) * -inf is NaN and no gradient through it exists, so the heads count such a row as bad as well
+// (include/mfg_learn.h: zero gradients for the element, a NaN loss): row_max_expsum's two passes with the smallest
+// l[j] - mx kept beside the sum (one more instruction per logit, no further load; mx and s are the same bits).
+__device__ __forceinline__ bool row_lse_finite(const float* __restrict__ l, int n, float& lse) {
+  float mx = l[0];
+  for (int j = 1; j < n; j++) mx = fmaxf(mx, l[j]);
+  float s = 0.0f, lo = 0.0f;
+  for (int j = 0; j < n; j++) {
+    const float d = l[j] - mx;
+    s += expf(d);
+    lo = fminf(lo, d);
+  }
+  lse = mx + logf(s);
+  return s > 0.0f && !isinf(s) && !isinf(mx) && !isinf(lo);
 }
 
 // The action of a row with valid mx / s (row_max_expsum): greedy: the argmax, lowest index on ties; otherwise the

@@ -89,19 +89,15 @@ __global__ void __launch_bounds__(256) k_ppo_head(const float* __restrict__ logi
     const float* q = old_logits + i * orow;
     float* dl = dlogits + i * drow;
     const int a = action[i];
-    float mx, s, qmx, qs;
-    row_max_expsum(l, n_act, mx, s);
-    row_max_expsum(q, n_act, qmx, qs);
-    // fmaxf drops a NaN operand, the sums keep it: s and qs are finite and positive exactly when every logit is
-    const bool ok = a >= 0 && a < n_act && s > 0.0f && qs > 0.0f && !isinf(s) && !isinf(qs) && !isinf(mx) &&
-                    !isinf(qmx);
+    float lse, qlse;
+    const bool fin = row_lse_finite(l, n_act, lse), qfin = row_lse_finite(q, n_act, qlse);  // every logit finite
+    const bool ok = a >= 0 && a < n_act && fin && qfin;
     if (!ok) {  // no indexing by a: zero gradients, and a NaN term makes the loss NaN
       for (int j = 0; j < n_act; j++) dl[j] = 0.0f;
       dcritic[i] = 0.0f;
       sum += (double)NAN;
       continue;
     }
-    const float lse = mx + logf(s), qlse = qmx + logf(qs);
     const float rhat = (float)(((double)ret[i] - mean) / sd);
     const float adv = rhat - critic[i];
     const float ratio = expf((l[a] - lse) - (q[a] - qlse));

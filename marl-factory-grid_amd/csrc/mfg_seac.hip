@@ -75,14 +75,6 @@ __global__ void __launch_bounds__(256) k_project_grouped(const uint16_t* __restr
 // ---- the loss head
 struct Strides { int64_t step, env, agent; };
 
-// max and exp-sum of n logits; false when one of them is not finite (fmaxf drops a NaN operand, the sum keeps it)
-__device__ __forceinline__ bool softmax_stats(const float* __restrict__ l, int n, float& lse) {
-  float mx, s;
-  row_max_expsum(l, n, mx, s);
-  lse = mx + logf(s);
-  return s > 0.0f && !isinf(s) && !isinf(mx);
-}
-
 // Network j = blockIdx.y, its rows q < rows (cross: all n = A B rows, agent q / B; own: the B rows of agent j).
 // logits [nets][n][t + 1][n_max] (own: nets = 1, row = j B + q), critic alike without the last axis.
 // A block takes R = 256 / (t + 1) whole (network, row) pairs at a time, one thread per entry s <= t of a pair, so the
@@ -146,9 +138,9 @@ __global__ void __launch_bounds__(256) k_seac_head(const float* __restrict__ log
         const float* own = logits + (((int64_t)i * n + row) * t1 + s) * (int64_t)n_max;  // cross: behaviour network
         const int a = action[s * sa.step + b * sa.env + i * sa.agent];
         float lse, lse_own = 0.0f;
-        bool ok = softmax_stats(l, na, lse) && a >= 0 && a < na && na_ok;
+        bool ok = row_lse_finite(l, na, lse) && a >= 0 && a < na && na_ok;  // every logit of the head finite
         const bool off = cross && i != j;
-        if (off) ok = softmax_stats(own, na, lse_own) && ok;
+        if (off) ok = row_lse_finite(own, na, lse_own) && ok;
         if (!ok) {  // nothing indexed by a: zero gradients, and a NaN term in every loss the element enters
           for (int c = 0; c < n_max; c++) d[c] = 0.0f;
           s_pv += (double)NAN;

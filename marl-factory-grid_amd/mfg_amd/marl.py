@@ -977,14 +977,25 @@ def mappo_loss(out, old_logits, actions, reward, done, gamma, entropy_coef, vf_c
                             gamma, entropy_coef, vf_coef, clip_range)
 
 
+def nonfinite_to_nan(logits):
+    """0 for a row of finite logits [..., n], NaN for a row that holds an infinite or NaN one (a constant: no gradient).
+    Added to the row's log-probability, where x + 0 changes nothing, it gives the loss heads' tensor code the fused
+    heads' contract (include/mfg_learn.h): a -inf logit away from the action would otherwise count as probability 0 and
+    leave the loss finite."""
+    ok = torch.isfinite(logits).all(-1)
+    return torch.where(ok, logits.new_zeros(()), logits.new_full((), float('nan')))
+
+
 def mappo_loss_terms(logits, critic, old_logits, actions, reward, done, gamma, entropy_coef, vf_coef, clip_range):
     """mappo_loss on the logits [N, T, n_act] and critic [N, T] of entries 0..T-1 and their actions [N, T]."""
     index = actions.unsqueeze(-1)
     old_log_probs = torch.gather(torch.log_softmax(old_logits, -1), dim=-1, index=index).squeeze(-1)
+    old_log_probs = old_log_probs + nonfinite_to_nan(old_logits)
     mc_returns = monte_carlo_returns(reward, done, gamma)
     mc_returns = (mc_returns - mc_returns.mean()) / (mc_returns.std() + 1e-8)
     advantages = mc_returns - critic
     log_ap = torch.gather(torch.log_softmax(logits, -1), dim=-1, index=index).squeeze(-1)
+    log_ap = log_ap + nonfinite_to_nan(logits)
     ratio = (log_ap - old_log_probs).exp()
     surr1 = ratio * advantages.detach()
     surr2 = torch.clamp(ratio, 1 - clip_range, 1 + clip_range) * advantages.detach()

@@ -22,7 +22,7 @@ import torch.nn.functional as F
 from torch.distributions import Categorical
 
 from . import learn_lib
-from .marl import RecurrentAC, _use_gru_kernels, compute_advantages
+from .marl import RecurrentAC, _use_gru_kernels, compute_advantages, nonfinite_to_nan
 
 _seac_lib = learn_lib.lib  # the former binder's name, for callers written against it
 
@@ -390,13 +390,14 @@ def iac_loss_terms(logits, critic, actions, reward, done, gamma, entropy_coef, v
     if n_act is None or all(int(c) == logits.shape[-1] for c in n_act):
         lp = torch.log_softmax(logits, -1)
         ent = Categorical(logits=logits, validate_args=False).entropy().mean((1, 2))
-        log_ap = torch.gather(lp, -1, actions.unsqueeze(-1)).squeeze(-1)
+        log_ap = torch.gather(lp, -1, actions.unsqueeze(-1)).squeeze(-1) + nonfinite_to_nan(logits)
     else:
         ents, laps = [], []
         for g in range(A):
             lg = logits[g, ..., :int(n_act[g])]
             ents.append(Categorical(logits=lg, validate_args=False).entropy().mean())
-            laps.append(torch.gather(torch.log_softmax(lg, -1), -1, actions[g].unsqueeze(-1)).squeeze(-1))
+            laps.append(torch.gather(torch.log_softmax(lg, -1), -1, actions[g].unsqueeze(-1)).squeeze(-1) +
+                        nonfinite_to_nan(lg))
         ent, log_ap = torch.stack(ents), torch.stack(laps)
     policy = -(adv.detach() * log_ap).mean((1, 2))
     if terms:
@@ -412,6 +413,7 @@ def seac_loss_terms(logits, critic, actions, reward, done, gamma, entropy_coef, 
     A = logits.shape[0]
     lp = torch.log_softmax(logits, -1)
     log_ap = torch.gather(lp, -1, actions[None].expand(A, *actions.shape).unsqueeze(-1)).squeeze(-1)  # [A, A, B, T]
+    log_ap = log_ap + nonfinite_to_nan(logits)  # NaN; in the row's own network it spoils every network's iw
     ar = torch.arange(A, device=logits.device)
     true_lp = log_ap[ar, ar]  # [A(agent), B, T]: the behaviour policy
     iw = (log_ap - true_lp[None]).exp().detach()
