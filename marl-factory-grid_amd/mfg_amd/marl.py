@@ -31,7 +31,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.distributions import Categorical
 
-from . import learn_lib
+from . import gru_window, learn_lib
 
 # the names of the former per-unit binders: callers written against them get the one binding
 _gru_lib = _ppo_lib = learn_lib.lib
@@ -351,128 +351,67 @@ def _packed_grads(idx, val, g, k):
 _DENSIFY_MAX_K = 4096  # mfg_packed_densify's bound on the dense row length (include/mfg_learn.h)
 
 
-def _use_gru_kernels(x):
-    """The learner's GRU window runs its elementwise steps as HIP kernels on the GPU (fp32); CPU tensors take the
-    tensor code (the same formulas)."""
-    return x.is_cuda and x.dtype == torch.float32
-
-
 class _GRUWindow(torch.autograd.Function):
     """Both GRUs of RecurrentAC (layer 0, PyTorch gate order r, z, n) over a window of T steps with per-entry
     restarts, forward and backward written out so the GEMMs are batched over the window:
       forward:  the input gates of every step and both GRUs as ONE GEMM [N*T, I] x [I, 3Ha + 3Hc]; per step the
-                recurrent gates h W_hh^T (one GEMM per GRU, the only sequential part);
-      backward: per step the recurrent chain dh W_hh (one GEMM per GRU), then ONE GEMM each for the input-weight
-                gradient of both GRUs, the input gradient, and per GRU one recurrent-weight gradient over all N*T
-                rows (autograd over T fused cells issues 4 GEMMs per step and GRU: 48 instead of 10 at T = 6).
+                recurrent gates h W_hh^T (one GEMM per GRU, the only sequential part: gru_window.forward_steps);
+      backward: _gru_pair_backward (autograd over T fused cells issues 4 GEMMs per step and GRU: 48 instead of 10 at
+                T = 6).
     keep [N, T]: the state entering step s is h_{s-1} * keep[:, s] (0 = an episode restart at s). h0 gets no
     gradient (the learner's carried state is detached, base_ac.py:126-128)."""
 
     @staticmethod
     def forward(ctx, x, keep, h0a, h0c, wia, wha, bia, bha, wic, whc, bic, bhc):
         n, t, i_dim = x.shape
-        ha_dim, hc_dim = wha.shape[1], whc.shape[1]
         wi = torch.cat([wia, wic], 0)  # [3Ha + 3Hc, I]
         bi = torch.cat([bia, bic], 0)
         gi = torch.addmm(bi, x.reshape(n * t, i_dim), wi.t()).view(n, t, -1)
-        outs, saved = [], []
-        if _use_gru_kernels(x):  # per step: the recurrent GEMM + one fused elementwise kernel (mfg_gru_fwd_step)
-            st = learn_lib.stream(x.device)
-            keep = keep.contiguous()
-            g_all = gi.shape[-1]
-            for (h, wh, bh, lo, hd) in ((h0a, wha, bha, 0, ha_dim), (h0c, whc, bhc, 3 * ha_dim, hc_dim)):
-                hs = torch.empty((n, t, hd), dtype=x.dtype, device=x.device)
-                sv = torch.empty((5, n, t, hd), dtype=x.dtype, device=x.device)  # hp, r, z, n, gh_n
-                bh = bh.contiguous()
-                hcur, h_row = h.contiguous(), hd
-                for s in range(t):
-                    gh0 = hcur @ wh.t()
-                    learn_lib.call('mfg_gru_fwd_step', gi[:, s, lo:].data_ptr(), t * g_all, gh0.data_ptr(),
-                                   bh.data_ptr(), hcur.data_ptr(), h_row, keep[:, s].data_ptr(), t,
-                                   hs[:, s].data_ptr(), t * hd, sv[0, :, s].data_ptr(), sv[1, :, s].data_ptr(),
-                                   sv[2, :, s].data_ptr(), sv[3, :, s].data_ptr(), sv[4, :, s].data_ptr(), t * hd, n,
-                                   hd, st)
-                    hcur, h_row = hs[:, s], t * hd
-                outs.append(hs)
-                saved += list(sv.unbind(0))
-            ctx.save_for_backward(x, keep, wi, wha, whc, *saved)
-            ctx.dims = (ha_dim, hc_dim)
-            return outs[0], outs[1]
-        for (h, wh, bh, lo, hd) in ((h0a, wha, bha, 0, ha_dim), (h0c, whc, bhc, 3 * ha_dim, hc_dim)):
-            hs, hps, rs, zs, ns, ghns = [], [], [], [], [], []
-            for s in range(t):
-                hp = h * keep[:, s:s + 1]
-                gh = torch.addmm(bh, hp, wh.t())
-                g = gi[:, s, lo:lo + 3 * hd]
-                r = torch.sigmoid(g[:, :hd] + gh[:, :hd])
-                z = torch.sigmoid(g[:, hd:2 * hd] + gh[:, hd:2 * hd])
-                ghn = gh[:, 2 * hd:]
-                nn_ = torch.tanh(g[:, 2 * hd:] + r * ghn)
-                h = nn_ + z * (hp - nn_)  # (1 - z) n + z h
-                hs.append(h); hps.append(hp); rs.append(r); zs.append(z); ns.append(nn_); ghns.append(ghn)
-            outs.append(torch.stack(hs, 1))
-            saved += [torch.stack(v, 1) for v in (hps, rs, zs, ns, ghns)]
+        outs, saved, lo = [], [], 0
+        for (h, wh, bh) in ((h0a, wha, bha), (h0c, whc, bhc)):
+            hd = wh.shape[1]
+            hs = torch.empty((n, t, hd), dtype=x.dtype, device=x.device)
+            sv = torch.empty((5, n, t, hd), dtype=x.dtype, device=x.device)  # hp, r, z, n, gh_n
+            gru_window.forward_steps(gi[:, :, lo:lo + 3 * hd], keep, h, wh, bh, hs, sv)
+            outs.append(hs)
+            saved += sv.unbind(0)
+            lo += 3 * hd
         ctx.save_for_backward(x, keep, wi, wha, whc, *saved)
-        ctx.dims = (ha_dim, hc_dim)
         return outs[0], outs[1]
 
     @staticmethod
     def backward(ctx, douta, doutc):
-        x, keep, wi, wha, whc, *saved = ctx.saved_tensors
-        ha_dim, hc_dim = ctx.dims
-        n, t, i_dim = x.shape
-        dgis, grads = [], []
-        gpu = _use_gru_kernels(x)
-        g_all = 3 * (ha_dim + hc_dim)
-        # GPU: both GRUs' input-gate gradients straight into one [n, t, 3Ha + 3Hc] buffer (no concatenation)
-        dgi_all = torch.empty((n, t, g_all), dtype=x.dtype, device=x.device) if gpu else None
-        for gi_idx, (dout, wh, hd) in enumerate(((douta, wha, ha_dim), (doutc, whc, hc_dim))):
-            hps, rs, zs, ns, ghns = saved[5 * gi_idx:5 * gi_idx + 5]
-            if gpu:  # per step: one fused elementwise kernel (mfg_gru_bwd_step) + the recurrent GEMM
-                st = learn_lib.stream(x.device)
-                dgi = dgi_all[:, :, 3 * ha_dim * gi_idx:]
-                dgh = torch.empty((n, t, 3 * hd), dtype=x.dtype, device=x.device)
-                dout = None if dout is None else dout.contiguous()
-                sv_row = hps.stride(0)
-                dhp = None
-                for s in range(t - 1, -1, -1):
-                    dhz = torch.empty((n, hd), dtype=x.dtype, device=x.device)
-                    learn_lib.call('mfg_gru_bwd_step', None if dout is None else dout[:, s].data_ptr(), t * hd,
-                                   learn_lib.ptr(dhp), None if dhp is None else keep[:, s + 1].data_ptr(), t,
-                                   rs[:, s].data_ptr(), zs[:, s].data_ptr(), ns[:, s].data_ptr(),
-                                   ghns[:, s].data_ptr(), hps[:, s].data_ptr(), sv_row, dgi[:, s].data_ptr(),
-                                   t * g_all, dgh[:, s].data_ptr(), t * 3 * hd, dhz.data_ptr(), n, hd, st)
-                    dhp = torch.addmm(dhz, dgh[:, s], wh)
-                dgh2 = dgh.reshape(n * t, 3 * hd)
-                grads.append((_tall_tn(dgh2, hps.reshape(n * t, hd)), dgh2.sum(0)))
-                continue
-            dgi = torch.empty((n, t, 3 * hd), dtype=x.dtype, device=x.device)
-            dgh = torch.empty_like(dgi)
-            carry = torch.zeros((n, hd), dtype=x.dtype, device=x.device)
-            for s in range(t - 1, -1, -1):
-                dh = carry if dout is None else dout[:, s] + carry
-                r, z, nn_, ghn, hp = rs[:, s], zs[:, s], ns[:, s], ghns[:, s], hps[:, s]
-                dn = dh * (1.0 - z) * (1.0 - nn_ * nn_)
-                dz = dh * (hp - nn_) * z * (1.0 - z)
-                dr = dn * ghn * r * (1.0 - r)
-                dgi[:, s, :hd] = dr
-                dgi[:, s, hd:2 * hd] = dz
-                dgi[:, s, 2 * hd:] = dn
-                dgh[:, s, :hd] = dr
-                dgh[:, s, hd:2 * hd] = dz
-                dgh[:, s, 2 * hd:] = dn * r
-                dhp = torch.addmm(dh * z, dgh[:, s], wh)  # dh z + dgh W_hh
-                carry = dhp * keep[:, s:s + 1]
-            dgis.append(dgi)
-            dgh2 = dgh.reshape(n * t, 3 * hd)
-            grads.append((_tall_tn(dgh2, hps.reshape(n * t, hd)), dgh2.sum(0)))  # dW_hh, db_hh
-        dgi_all = (dgi_all if gpu else torch.cat(dgis, 2)).reshape(n * t, -1)
-        dwi = _tall_tn(dgi_all, x.reshape(n * t, i_dim))  # [3Ha + 3Hc, I]
-        dbi = dgi_all.sum(0)
-        dx = (dgi_all @ wi).view(n, t, i_dim)
-        sa = 3 * ha_dim
-        return (dx, None, None, None, dwi[:sa], grads[0][0], dbi[:sa], grads[0][1],
-                dwi[sa:], grads[1][0], dbi[sa:], grads[1][1])
+        x, keep, wi, wha, whc, *sv = ctx.saved_tensors
+        g = _gru_pair_backward(x, keep, wi, (wha, whc), sv, (douta, doutc), entry_major=False)
+        return (g[0], None, None, None, *g[1:])
+
+
+def _gru_pair_backward(x, keep, wi, whs, sv, douts, entry_major):
+    """The backward of both GRUs over a window held batch-major ([N, T, ·]) or entry-major ([T, N, ·]): keep and the
+    ten saved activations sv (hp, r, z, n, gh_n per GRU) in that layout, x and douts (None: no gradient) with the same
+    rows in memory order. Per GRU and step the recurrent chain (gru_window.backward_steps), both GRUs' input-gate
+    gradients straight into one [.., .., 3Ha + 3Hc] buffer; then ONE GEMM each for the input-weight gradient of both
+    GRUs and the input gradient, and per GRU one recurrent-weight gradient, all over the window's N T rows.
+    Returns (dx, dW_ih, dW_hh, db_ih, db_hh of the actor GRU, the same of the critic GRU)."""
+    lead, m = keep.shape, keep.numel()
+    win = (lambda v: v.transpose(0, 1)) if entry_major else (lambda v: v)  # a buffer as its [rows, T, ·] window view
+    dgi_all = torch.empty((*lead, 3 * sum(wh.shape[1] for wh in whs)), dtype=x.dtype, device=x.device)
+    grads, lo = [], 0
+    for dout, wh, s5 in zip(douts, whs, (sv[:5], sv[5:])):
+        hd = wh.shape[1]
+        dgh = torch.empty((*lead, 3 * hd), dtype=x.dtype, device=x.device)
+        dout = None if dout is None else win(dout.contiguous().view(*lead, hd))
+        gru_window.backward_steps(dout, win(keep), [win(v) for v in s5], wh, win(dgi_all)[:, :, lo:lo + 3 * hd],
+                                  win(dgh))
+        dgh2 = dgh.view(m, 3 * hd)
+        grads.append((_tall_tn(dgh2, s5[0].reshape(m, hd)), dgh2.sum(0)))  # dW_hh, db_hh
+        lo += 3 * hd
+    dgi2 = dgi_all.view(m, -1)
+    dwi = _tall_tn(dgi2, x.reshape(m, -1))  # [3Ha + 3Hc, I]
+    dbi = dgi2.sum(0)
+    sa = 3 * whs[0].shape[1]
+    return ((dgi2 @ wi).view_as(x), dwi[:sa], grads[0][0], dbi[:sa], grads[0][1], dwi[sa:], grads[1][0], dbi[sa:],
+            grads[1][1])
 
 
 class _MixSaved(torch.autograd.Function):
@@ -509,8 +448,7 @@ class _GRUWindowSavedT(torch.autograd.Function):
     """Both GRUs over a window whose forward the acting steps already ran (mfg_gru_fwd_step) with the same weights,
     entry-major: saved = (hs_a, hs_c, sv_a, sv_c), outputs [T, N, H] and gate activations [5, T, N, H] (hp, r, z, n,
     gh_n); x [T*N, I] the GRUs' input, keep [T, N] (0 = an episode restart at that entry). The forward returns the
-    stored outputs; the backward is _GRUWindow's (per step one mfg_gru_bwd_step and the recurrent GEMM, then one GEMM
-    each for the input-weight, input and recurrent-weight gradients over all T*N rows) on entry-major rows."""
+    stored outputs; the backward is _GRUWindow's (_gru_pair_backward) on entry-major rows."""
 
     @staticmethod
     def forward(ctx, x, keep, saved, wia, wha, bia, bha, wic, whc, bic, bhc):
@@ -523,34 +461,8 @@ class _GRUWindowSavedT(torch.autograd.Function):
     @staticmethod
     def backward(ctx, douta, doutc):
         x, keep, wi, wha, whc, *sv = ctx.saved_tensors
-        t, n = keep.shape
-        ha_dim, hc_dim = wha.shape[1], whc.shape[1]
-        g_all = 3 * (ha_dim + hc_dim)
-        st = learn_lib.stream(x.device)
-        dgi_all = torch.empty((t, n, g_all), dtype=x.dtype, device=x.device)
-        grads = []
-        for gidx, (dout, wh, hd) in enumerate(((douta, wha, ha_dim), (doutc, whc, hc_dim))):
-            hps, rs, zs, ns, ghns = sv[5 * gidx:5 * gidx + 5]
-            dgh = torch.empty((t, n, 3 * hd), dtype=x.dtype, device=x.device)
-            dout = None if dout is None else dout.contiguous().view(t, n, hd)
-            lo = 3 * ha_dim * gidx
-            dhp = None
-            for s in range(t - 1, -1, -1):
-                dhz = torch.empty((n, hd), dtype=x.dtype, device=x.device)
-                learn_lib.call('mfg_gru_bwd_step', None if dout is None else dout[s].data_ptr(), hd,
-                               learn_lib.ptr(dhp), None if dhp is None else keep[s + 1].data_ptr(), 1,
-                               rs[s].data_ptr(), zs[s].data_ptr(), ns[s].data_ptr(), ghns[s].data_ptr(),
-                               hps[s].data_ptr(), hd, dgi_all[s, :, lo:].data_ptr(), g_all, dgh[s].data_ptr(), 3 * hd,
-                               dhz.data_ptr(), n, hd, st)
-                dhp = torch.addmm(dhz, dgh[s], wh)
-            dgh2 = dgh.view(t * n, 3 * hd)
-            grads.append((_tall_tn(dgh2, hps.reshape(t * n, hd)), dgh2.sum(0)))
-        dgi2 = dgi_all.view(t * n, g_all)
-        dwi, dbi = _tall_tn(dgi2, x), dgi2.sum(0)
-        dx = dgi2 @ wi
-        sa = 3 * ha_dim
-        return (dx, None, None, dwi[:sa], grads[0][0], dbi[:sa], grads[0][1], dwi[sa:], grads[1][0], dbi[sa:],
-                grads[1][1])
+        g = _gru_pair_backward(x, keep, wi, (wha, whc), sv, (douta, doutc), entry_major=True)
+        return (g[0], None, None, *g[1:])
 
 
 def _gru_cell(gi, h, gru):
@@ -758,20 +670,15 @@ class BatchedA2C:
 
     def _gru_step(self, x, t):
         """Both GRU cells of entry t on x [N, I] (one input-gate GEMM for both, one recurrent GEMM and one
-        mfg_gru_fwd_step each), storing outputs and activations at entry t of the window buffers."""
-        net, N, T = self.net, self.N, self.T
-        ga, gc = net.gru_actor, net.gru_critic
+        forward step each: gru_window.forward_steps on a window of that one entry, no restart), storing outputs and
+        activations at entry t of the entry-major window buffers."""
+        ga, gc = self.net.gru_actor, self.net.gru_critic
         gi = torch.addmm(torch.cat([ga.bias_ih_l0, gc.bias_ih_l0]), x, torch.cat([ga.weight_ih_l0, gc.weight_ih_l0]).t())
-        st = learn_lib.stream(self.dev)
-        lo = 0
+        gi, keep, lo = gi[:, None], self._one.expand(self.N, 1), 0
         for (h, gru, hs, sv) in ((self.ha, ga, self.hs_a, self.sv_a), (self.hc, gc, self.hs_c, self.sv_c)):
             hd = hs.shape[-1]
-            h2 = h[:, 0]
-            gh0 = h2 @ gru.weight_hh_l0.t()
-            learn_lib.call('mfg_gru_fwd_step', gi[:, lo:].data_ptr(), gi.shape[1], gh0.data_ptr(),
-                           gru.bias_hh_l0.data_ptr(), h2.data_ptr(), hd, self._one.data_ptr(), 0, hs[t].data_ptr(), hd,
-                           sv[0, t].data_ptr(), sv[1, t].data_ptr(), sv[2, t].data_ptr(), sv[3, t].data_ptr(),
-                           sv[4, t].data_ptr(), hd, N, hd, st)
+            gru_window.forward_steps(gi[:, :, lo:lo + 3 * hd], keep, h[:, 0], gru.weight_hh_l0, gru.bias_hh_l0,
+                                     hs[t:t + 1].transpose(0, 1), sv[:, t:t + 1].transpose(1, 2))
             lo += 3 * hd
 
     def _sample(self, logits, t):

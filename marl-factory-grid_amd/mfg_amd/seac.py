@@ -21,8 +21,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.distributions import Categorical
 
-from . import learn_lib
-from .marl import RecurrentAC, _use_gru_kernels, compute_advantages, nonfinite_to_nan
+from . import gru_window, learn_lib
+from .gru_window import blin as _blin  # per-agent x W^T + b, the layers' GEMM (and the grouped GRU step's)
+from .marl import RecurrentAC, compute_advantages, nonfinite_to_nan
 
 _seac_lib = learn_lib.lib  # the former binder's name, for callers written against it
 
@@ -32,16 +33,6 @@ _PAD_KEYS = ('action_emb.weight', 'action_head.2.weight', 'action_head.2.bias') 
 def seac_ws_bytes(n_agents):
     """MFG_SEAC_WS_BYTES(g) (include/mfg_learn.h)."""
     return 4096 * n_agents
-
-
-def _blin(x, w, b):
-    """Per-agent x W^T + b: x [A, M, in], w [A, out, in], b [A, out] -> [A, M, out]: one baddbmm over agents on the
-    GPU; on the CPU one addmm per agent, the very call of RecurrentAC's layers (a batched GEMM there rounds in another
-    order, and the CPU forward is pinned bit-equal to the separate modules; the operands are copied out of the stack
-    because the CPU GEMM's summation order also depends on their alignment)."""
-    if not x.is_cuda:
-        return torch.stack([torch.addmm(b[g].clone(), x[g].clone(), w[g].clone().t()) for g in range(x.shape[0])])
-    return torch.baddbmm(b[:, None], x, w.transpose(1, 2))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -120,84 +111,35 @@ class _GroupedProj(torch.autograd.Function):
 # one GRU of every network over a window
 # ---------------------------------------------------------------------------------------------------------------------
 class _GRUWindowG(torch.autograd.Function):
-    """marl._GRUWindow for one GRU of A networks: gi [A, n, T, 3hd] (the input gates, with grad), keep [A, n, T]
-    (0 = a restart at that entry), h0 [A, n, hd] (no gradient), wh [A, 3hd, hd], bh [A, 3hd] -> hs [A, n, T, hd].
-    Per step one bmm over agents and one elementwise kernel on the GPU (mfg_gru_fwd_step_grouped: the recurrent bias
-    of a row is its agent block's; mfg_gru_bwd_step reads no bias and runs over all A n rows at once)."""
+    """One GRU of A networks over a window: gi [A, n, T, 3hd] (the input gates, with grad), keep [A, n, T] (0 = a
+    restart at that entry), h0 [A, n, hd] (no gradient), wh [A, 3hd, hd], bh [A, 3hd] -> hs [A, n, T, hd]. The
+    recurrence is gru_window's on the A n rows with the stacked weight (per step one bmm over agents and, on the GPU,
+    one elementwise kernel: mfg_gru_fwd_step_grouped takes a row's recurrent bias from its agent block, mfg_gru_bwd_step
+    reads no bias); the recurrent-weight gradient is one bmm over the window."""
 
     @staticmethod
     def forward(ctx, gi, keep, h0, wh, bh):
         A, n, T, g3 = gi.shape
         hd = g3 // 3
-        whT = wh.transpose(1, 2)
-        if _use_gru_kernels(gi):
-            st = learn_lib.stream(gi.device)
-            if gi.stride(3) != 1 or gi.stride(2) < g3 or gi.stride(1) != T * gi.stride(2) or \
-                    gi.stride(0) != n * gi.stride(1):
-                gi = gi.contiguous()  # (a column slice of both GRUs' gates is read in place)
-            keep, bh = keep.contiguous(), bh.contiguous()
-            hs = torch.empty((A, n, T, hd), dtype=gi.dtype, device=gi.device)
-            sv = torch.empty((5, A, n, T, hd), dtype=gi.dtype, device=gi.device)  # hp, r, z, n, gh_n
-            hcur, h_row = h0.contiguous(), hd
-            for s in range(T):
-                gh0 = torch.bmm(hcur, whT)  # [A, n, 3hd]
-                learn_lib.call('mfg_gru_fwd_step_grouped', gi[:, :, s].data_ptr(), gi.stride(1), gh0.data_ptr(),
-                               bh.data_ptr(), n, hcur.data_ptr(), h_row, keep[:, :, s].data_ptr(), T,
-                               hs[:, :, s].data_ptr(), T * hd, sv[0, :, :, s].data_ptr(), sv[1, :, :, s].data_ptr(),
-                               sv[2, :, :, s].data_ptr(), sv[3, :, :, s].data_ptr(), sv[4, :, :, s].data_ptr(), T * hd,
-                               A * n, hd, st)
-                hcur, h_row = hs[:, :, s], T * hd
-            saved = list(sv.unbind(0))
-        else:
-            h = h0
-            cols = [[] for _ in range(6)]
-            for s in range(T):
-                hp = h * keep[:, :, s:s + 1]
-                gh = _blin(hp, wh, bh)
-                g = gi[:, :, s]
-                r = torch.sigmoid(g[..., :hd] + gh[..., :hd])
-                z = torch.sigmoid(g[..., hd:2 * hd] + gh[..., hd:2 * hd])
-                ghn = gh[..., 2 * hd:]
-                nn_ = torch.tanh(g[..., 2 * hd:] + r * ghn)
-                h = nn_ + z * (hp - nn_)
-                for c, v in zip(cols, (h, hp, r, z, nn_, ghn)):
-                    c.append(v)
-            hs = torch.stack(cols[0], 2)
-            saved = [torch.stack(c, 2) for c in cols[1:]]
-        ctx.save_for_backward(keep, wh, *saved)
+        if gru_window.use_kernels(gi) and (gi.stride(3) != 1 or gi.stride(0) != n * gi.stride(1)):
+            gi = gi.contiguous()  # (a column slice of both GRUs' gates is read in place)
+        hs = torch.empty((A, n, T, hd), dtype=gi.dtype, device=gi.device)
+        sv = torch.empty((5, A, n, T, hd), dtype=gi.dtype, device=gi.device)  # hp, r, z, n, gh_n
+        gru_window.forward_steps(gi.flatten(0, 1), keep.flatten(0, 1), h0.flatten(0, 1), wh, bh, hs.flatten(0, 1),
+                                 sv.flatten(1, 2))
+        ctx.save_for_backward(keep, wh, *sv.unbind(0))
         return hs
 
     @staticmethod
     def backward(ctx, dout):
-        keep, wh, hps, rs, zs, ns, ghns = ctx.saved_tensors
-        A, n, T, hd = hps.shape
-        dgi = torch.empty((A, n, T, 3 * hd), dtype=hps.dtype, device=hps.device)
+        keep, wh, *sv = ctx.saved_tensors
+        A, n, T, hd = sv[0].shape
+        dgi = torch.empty((A, n, T, 3 * hd), dtype=dout.dtype, device=dout.device)
         dgh = torch.empty_like(dgi)
-        if _use_gru_kernels(hps):
-            st = learn_lib.stream(hps.device)
-            dout = dout.contiguous()
-            dhp = None
-            for s in range(T - 1, -1, -1):
-                dhz = torch.empty((A, n, hd), dtype=hps.dtype, device=hps.device)
-                learn_lib.call('mfg_gru_bwd_step', dout[:, :, s].data_ptr(), T * hd, learn_lib.ptr(dhp),
-                               None if dhp is None else keep[:, :, s + 1].data_ptr(), T, rs[:, :, s].data_ptr(),
-                               zs[:, :, s].data_ptr(), ns[:, :, s].data_ptr(), ghns[:, :, s].data_ptr(),
-                               hps[:, :, s].data_ptr(), T * hd, dgi[:, :, s].data_ptr(), T * 3 * hd,
-                               dgh[:, :, s].data_ptr(), T * 3 * hd, dhz.data_ptr(), A * n, hd, st)
-                dhp = torch.baddbmm(dhz, dgh[:, :, s], wh)
-        else:
-            carry = torch.zeros((A, n, hd), dtype=hps.dtype, device=hps.device)
-            for s in range(T - 1, -1, -1):
-                dh = dout[:, :, s] + carry
-                r, z, nn_, ghn, hp = rs[:, :, s], zs[:, :, s], ns[:, :, s], ghns[:, :, s], hps[:, :, s]
-                dn = dh * (1.0 - z) * (1.0 - nn_ * nn_)
-                dz = dh * (hp - nn_) * z * (1.0 - z)
-                dr = dn * ghn * r * (1.0 - r)
-                dgi[:, :, s] = torch.cat([dr, dz, dn], -1)
-                dgh[:, :, s] = torch.cat([dr, dz, dn * r], -1)
-                carry = torch.baddbmm(dh * z, dgh[:, :, s], wh) * keep[:, :, s:s + 1]
+        gru_window.backward_steps(dout.contiguous().flatten(0, 1), keep.flatten(0, 1), [v.flatten(0, 1) for v in sv],
+                                  wh, dgi.flatten(0, 1), dgh.flatten(0, 1))
         dgh2 = dgh.view(A, n * T, 3 * hd)
-        return dgi, None, None, torch.bmm(dgh2.transpose(1, 2), hps.reshape(A, n * T, hd)), dgh2.sum(1)
+        return dgi, None, None, torch.bmm(dgh2.transpose(1, 2), sv[0].reshape(A, n * T, hd)), dgh2.sum(1)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

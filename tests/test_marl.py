@@ -382,9 +382,10 @@ def test_gru_window_kernels_match_tensor_code(monkeypatch):
     h0 = torch.randn(n, 1, 16, device='cuda')
     starts = torch.rand(n, t, device='cuda') < 0.1
     res = {}
-    orig = M._use_gru_kernels
+    from mfg_amd import gru_window
+    orig = gru_window.use_kernels
     for kern in (True, False):
-        monkeypatch.setattr(M, '_use_gru_kernels', orig if kern else (lambda x: False))  # restored on failure too
+        monkeypatch.setattr(gru_window, 'use_kernels', orig if kern else (lambda x: False))  # restored on failure too
         net.zero_grad()
         out = net.forward_emb(emb, acts, h0, h0, starts=starts)
         (out['logits'].square().sum() + out['critic'].sum()).backward()
