@@ -290,6 +290,8 @@ typedef struct mfg_variant {
                                  engine's second stream beside the render): per-kernel times for attribution */
   int32_t obs_generic;        /* 1: dense obs of pomdp_r 1..3 through the generic render (window geometry read from the
                                  spec at run time) instead of the one compiled for that radius: parity and A/B runs */
+  int32_t obs_wide_records;   /* 1: the folded render of specs with at most 16 agents keeps the three-word cell and layer
+                                 records (the ones of wider specs) instead of the one-word ones: parity runs */
 } mfg_variant;
 int mfg_create_variant(const mfg_spec* spec, int device, int64_t n_envs, const mfg_variant* variant,
                        mfg_engine** out);

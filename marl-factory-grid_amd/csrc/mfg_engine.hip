@@ -34,6 +34,7 @@ struct mfg_engine {
   int obs_nwv = 1;          // waves per env of the render (> 1: multi-wave render, k_obs_mw)
   bool replay2 = false;     // two-wave replay (k_replay2) for floor lists whose 1-wave slice fills a SIMD
   int obs_geo_r = 0;        // > 0: dense obs through the render with this pomdp_r's window geometry folded (ObsGeo)
+  int obs_narrow = 0;       // 1: ... and with one-word cell and layer records (at most 16 agents; build_obs, NARROW)
   struct Mark { int k; hipEvent_t a, b; };
   std::vector<Mark> marks;
   std::string err;  // mfg_last_error(e)
@@ -332,7 +333,7 @@ extern "C" int mfg_create_variant(const mfg_spec* s, int device, int64_t n_envs,
   if (!s || !out) return fail("null argument");
   if (n_envs < 1) return fail("n_envs must be >= 1");
   if (validate_spec(s)) return -1;
-  const mfg_variant none{0, 0, 0, 0, 0, 0, 0};
+  const mfg_variant none{0, 0, 0, 0, 0, 0, 0, 0};
   DevGuard g(device);
   return create_impl(s, device, n_envs, v ? *v : none, out);
 }
@@ -732,6 +733,9 @@ static int create_impl(const mfg_spec* s, int device, int64_t n_envs, const mfg_
         h.maxpts == 2 * R + 2 && h.nrays == NRAYS[R - 1] && h.A <= MFG_WAVE)
       e->obs_geo_r = R;
   }
+  // ... with one-word records when every agent has a bit in the 16-bit agent field (mfg_variant.obs_wide_records:
+  // never)
+  e->obs_narrow = MFG_OBS_NARROW && e->obs_geo_r > 0 && h.A <= 16 && !v.obs_wide_records;
   {  // k_resetdone's grid: the waves resident at once (one round; each strides over the done list)
     const int wpb = wpb_for(h.lds_full);
     int per_cu = 0, n_cu = 0;
@@ -818,7 +822,8 @@ extern "C" int mfg_destroy(mfg_engine* e) {
 // record layout for host-side decoding (tests, snapshots):
 // [size, o_hdr, ..., o_perm, lmax, obs_agent_stride, lds_full, xchg_ordered, o_machines, ..., scratch_bytes, o_logic,
 //  reset_overlap (1: with auto-reset and obs, a step's resets and their render run on the engine's second stream),
-//  obs_geo_r (> 0: dense obs are rendered by the kernels with this pomdp_r's window geometry folded, 0: the generic ones)]
+//  obs_geo_r (> 0: dense obs are rendered by the kernels with this pomdp_r's window geometry folded, 0: the generic ones),
+//  obs_narrow (1: the folded render with one-word cell and layer records)]
 extern "C" int mfg_layout(const mfg_engine* e, int32_t* out) {
   const MfgLayout& L = e->h.L;
   const int32_t v[] = {L.size, L.o_hdr, L.o_rule_ctr, L.o_agent_pos, L.o_agent_arr, L.o_agent_par, L.o_frozen_org,
@@ -827,7 +832,7 @@ extern "C" int mfg_layout(const mfg_engine* e, int32_t* out) {
                        e->h.lmax, e->h.obs_agent_stride, e->h.lds_full, e->h.xchg_ordered, L.o_machines,
                        L.o_maints, L.o_mstate, L.o_mpath, L.o_grank, e->h.dirt_cap, e->h.lds_logic, e->h.lds_obs,
                        e->h.lds_replay_per_wave, e->h.bfs_off, e->h.bfs_bytes, e->h.max_pairs, e->h.scratch_bytes,
-                       L.o_logic, e->overlap ? 1 : 0, e->obs_geo_r};
+                       L.o_logic, e->overlap ? 1 : 0, e->obs_geo_r, e->obs_narrow};
   const int n = (int)(sizeof(v) / sizeof(v[0]));
   for (int i = 0; i < n; i++) out[i] = v[i];
   return n;
@@ -874,7 +879,12 @@ static hipError_t launch_obs_t(mfg_engine* e, OT* obs, const ObsPacked& pk, hipS
   L.dirt = e->h.dirt_cap != 0;
   if constexpr (PK == 0 && (MP == 4 || MP == 6 || MP == 8)) {
     constexpr int R = MP / 2 - 1;
-    if (e->obs_geo_r == R && !L.mw) return launch_obs_geo<R, OT>(L, obs, st, skip, list);
+    if (e->obs_geo_r == R && !L.mw) {
+#if MFG_OBS_NARROW
+      if (e->obs_narrow) return launch_obs_geo<R, OT, true>(L, obs, st, skip, list);  // mfg_obs_h.hip
+#endif
+      return launch_obs_geo<R, OT, false>(L, obs, st, skip, list);
+    }
   }
   return launch_obs_inst<MP, OT, PK>(L, obs, pk, st, skip, list);
 }

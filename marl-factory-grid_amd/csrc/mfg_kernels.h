@@ -2647,12 +2647,26 @@ struct ObsGeo {
   static constexpr int maxpts = 2 * R + 2;                       // points per ray: fr + 1, the MAXPTS bucket
   static constexpr int nrays = R == 1 ? 24 : (R == 2 ? 38 : 44);  // unique ray targets of radius 2R + 1 (R <= 3)
 };
-template <int MAXPTS, typename OT, bool MM, int PK, bool DIRT, bool MW, int R = 0>
+// NARROW (folded render, specs with at most 16 agents: mfg_create, obs_narrow): one u32 per window cell and one per
+// layer instead of three each, so the flattened pass reads one LDS word and one ds_bpermute per run and counts with
+// one popc:
+//   cell word  (ctag[c]):  bits 0..8 tags | bits 9..24 the agents visible on the cell | bit 25 the cell's door is closed
+//   layer word (lane l):   bits 0..8 unit tags | bits 9..24 agent bits | bits 26..31 the LR_* flags
+// cell & layer has no bit outside 0..24 (the cell word ends at bit 25, which no layer word has), so the count is
+// popc(cell & layer). The lane-per-agent scatter ORs into the cell words; the amw pair table is not touched.
+#ifndef MFG_OBS_NARROW
+#define MFG_OBS_NARROW 1  // 0: every folded render keeps the three-word records
+#endif
+#define NC_AG_SHIFT 9
+#define NC_CLOSED (1u << 25)
+#define NC_FL_SHIFT 26
+template <int MAXPTS, typename OT, bool MM, int PK, bool DIRT, bool MW, int R = 0, bool NARROW_ = false>
 __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPacked& pk, int wv, int nwv,
                           int slot = 0) {
   SpecP S = e.S;
   constexpr bool LR = MAXPTS == 0;
   constexpr bool GEO = R > 0;
+  static_assert(!NARROW_ || GEO, "narrow records: the folded render only");
   static_assert(!GEO || (R <= 3 && MAXPTS == ObsGeo<R>::maxpts && PK == 0 && !MW), "folded window geometry");
   typedef ObsGeo<GEO ? R : 1> G;
   constexpr int RMP = LR ? 2 : MAXPTS;  // RayLane width (unused by the long-ray walk)
@@ -2721,6 +2735,8 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
   constexpr bool FLAT = MFG_OBS_FLAT && (LR || MAXPTS <= MFG_OBS_FLAT_MAXPTS) &&
                         (PK == 0 || (MFG_OBS_FLAT_PK && (LR || MAXPTS > 8)));
   tu32* ctag = pq + 2 * MFG_WAVE;
+  constexpr bool NARROW = NARROW_ && FLAT && MFG_OBS_NARROW;
+  static_assert(!NARROW || (MFG_TAG_MAINTAINERS < NC_AG_SHIFT && !LR && PK == 0), "narrow cell word");
   constexpr bool has_dirt = DIRT;  // S->dirt_cap != 0 (a template parameter: the register budget of k_obs)
   const float invW = 1.0f / (float)W;
   // lane-distributed copies of the small tables (uniform loops read them with v_readlane); agents 64.. of wide specs
@@ -2783,14 +2799,20 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
     for (int i = lane; i < OBS_FV_WORDS; i += MFG_WAVE) fv[i] = 0xFFFFFFFFu;
     for (int i = lane; i < nsup4; i += MFG_WAVE) ((uint32_t*)wsup)[i] = 0u;
     for (int i = lane; i < ndsup; i += MFG_WAVE) dsup[i] = 0u;
-    for (int i = lane; i < (wide ? 4 : 2) * dd; i += MFG_WAVE) amw[i] = 0u;
+    if constexpr (NARROW) {
+      for (int i = lane; i < dd; i += MFG_WAVE) ctag[i] = 0u;
+    } else {
+      for (int i = lane; i < (wide ? 4 : 2) * dd; i += MFG_WAVE) amw[i] = 0u;
+    }
     if (has_dirt)
       for (int i = lane; i < dd; i += MFG_WAVE) wdirt[i] = 0u;
     tbl_sync<LR>();
     if (lane < A) {  // scatter the agents into the window's agent masks
       const int wx = agx - wx0, wy = agy - wy0;
-      if ((unsigned)wx < (unsigned)oh && (unsigned)wy < (unsigned)ow)
-        atomicOr((uint32_t*)&amw[2 * (wx * ow + wy) + (lane >> 5)], 1u << (lane & 31));
+      if ((unsigned)wx < (unsigned)oh && (unsigned)wy < (unsigned)ow) {
+        if constexpr (NARROW) atomicOr((uint32_t*)&ctag[wx * ow + wy], 1u << (NC_AG_SHIFT + lane));  // A <= 16
+        else atomicOr((uint32_t*)&amw[2 * (wx * ow + wy) + (lane >> 5)], 1u << (lane & 31));
+      }
     }
     if (wide && lane + MFG_WAVE < A) {  // agents 64..127
       const int p2 = e.agpos()[lane + MFG_WAVE];
@@ -2976,9 +2998,14 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
     {
       const MfgLayerRec CS* lr = (const MfgLayerRec CS*)S->lrec + (size_t)a * S->lmax;
       if (lane < nl) {
-        lr_tf = (lr[lane].unit_tags & 0xFFFFu) | (lr[lane].flags << 16);
-        lr_alo = (uint32_t)lr[lane].agent_bits;
-        lr_ahi = (uint32_t)(lr[lane].agent_bits >> 32);
+        if constexpr (NARROW) {  // one word (agents 0..15: the spec has no others)
+          lr_tf = (lr[lane].unit_tags & ((1u << NC_AG_SHIFT) - 1u)) |
+                  (((uint32_t)lr[lane].agent_bits & 0xFFFFu) << NC_AG_SHIFT) | (lr[lane].flags << NC_FL_SHIFT);
+        } else {
+          lr_tf = (lr[lane].unit_tags & 0xFFFFu) | (lr[lane].flags << 16);
+          lr_alo = (uint32_t)lr[lane].agent_bits;
+          lr_ahi = (uint32_t)(lr[lane].agent_bits >> 32);
+        }
       }
     }
     // packed mode: entry count so far and the projection accumulators (lane j holds outputs j, 64 + j, ...)
@@ -3087,7 +3114,9 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
         tags = di ? (tags | (1u << MFG_TAG_DIRT)) : (tags & ~(1u << MFG_TAG_DIRT));
       }
       const int wic = inwin ? wi : 0;
-      const u64 amraw = (u64)amw[2 * wic] | ((u64)amw[2 * wic + 1] << 32);
+      u64 amraw;
+      if constexpr (NARROW) amraw = (u64)(((uint32_t)ctag[wic] >> NC_AG_SHIFT) & 0xFFFFu);
+      else amraw = (u64)amw[2 * wic] | ((u64)amw[2 * wic + 1] << 32);
       const u64 amask = v ? amraw : 0ull;
       // tag value: entity encodings (walls/agents/items/pods/drop-offs/destinations 1, doors 0.6666 closed /
       // 0.4444 open, dirt = amount)
@@ -3103,7 +3132,11 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
         if (tag == MFG_TAG_MACHINES) return (double)S->s.machine_pause;  // idle forever: encoding 15 (Q18)
         return 1.0;
       };
-      if constexpr (FLAT) {  // stash: the flattened pass below writes the layers (each lane only its own cell here)
+      if constexpr (NARROW) {  // stash, one word: tags, the visible agents, door closed
+        ctag[wi] = tags | ((uint32_t)amask << NC_AG_SHIFT) | ((m & CM_DCLOSED) ? NC_CLOSED : 0u);
+        if (has_dirt) wdirt[wi] = v ? wdirt[wi] : 0u;
+        continue;
+      } else if constexpr (FLAT) {  // stash: the flattened pass below writes the layers (each lane only its own cell here)
         ctag[wi] = tags | ((m & CM_DCLOSED) ? CT_CLOSED : 0u);
         amw[2 * wi] = (uint32_t)amask;
         amw[2 * wi + 1] = (uint32_t)(amask >> 32);
@@ -3214,15 +3247,28 @@ __device__ void build_obs(const Env& e, OT* out_env, int* pair_glob, const ObsPa
       for (int e0 = e_first; e0 < ne; e0 += MFG_WAVE) {
         const int el = min((GEO && MFG_OBS_GEO_ALIGN > 0) ? max(e0 + lane, 0) : e0 + lane, ne - 1);
         const int l = (int)(((float)el + 0.5f) * invdd), c = el - l * dd;
-        const uint32_t ct = ctag[c];
-        const u64 am = (u64)amw[2 * c] | ((u64)amw[2 * c + 1] << 32);
-        const uint32_t tf = bperm(l, lr_tf);
-        const uint64_t ab = (uint64_t)bperm(l, lr_alo) | ((uint64_t)bperm(l, lr_ahi) << 32);
-        const uint32_t ut = tf & 0xFFFFu, fl = tf >> 16;
-        int cnt = popc(ct & ut) + popc(am & ab);
-        if (wide) {  // agents 64..127: layer l's second agent word (per-lane load) against the second mask table
-          const uint64_t ab2 = S->lrec_ab2[(size_t)a * S->lmax + l];
-          cnt += popc(((u64)amw2[2 * c] | ((u64)amw2[2 * c + 1] << 32)) & ab2);
+        uint32_t ct, fl;
+        u64 am;
+        int cnt;
+        if constexpr (NARROW) {
+          const uint32_t cw = ctag[c], rec = bperm(l, lr_tf);
+          cnt = popc(cw & rec);
+          fl = rec >> NC_FL_SHIFT;
+          // the three-word view of the cell, for the flagged layers below
+          ct = (cw & ((1u << NC_AG_SHIFT) - 1u)) | ((cw & NC_CLOSED) ? CT_CLOSED : 0u);
+          am = (u64)((cw >> NC_AG_SHIFT) & 0xFFFFu);
+        } else {
+          ct = ctag[c];
+          am = (u64)amw[2 * c] | ((u64)amw[2 * c + 1] << 32);
+          const uint32_t tf = bperm(l, lr_tf);
+          const uint64_t ab = (uint64_t)bperm(l, lr_alo) | ((uint64_t)bperm(l, lr_ahi) << 32);
+          const uint32_t ut = tf & 0xFFFFu;
+          fl = tf >> 16;
+          cnt = popc(ct & ut) + popc(am & ab);
+          if (wide) {  // agents 64..127: layer l's second agent word (per-lane load) against the second mask table
+            const uint64_t ab2 = S->lrec_ab2[(size_t)a * S->lmax + l];
+            cnt += popc(((u64)amw2[2 * c] | ((u64)amw2[2 * c + 1] << 32)) & ab2);
+          }
         }
         OT out = (OT)cnt;  // a small count: exact in OT
         if (fl) {
@@ -3707,7 +3753,7 @@ k_resetdone(const MfgDevSpec* S_, uint8_t* state, long long B, int rd_slot) {
 // Observation render of every env into obs[env] (read-only on the state). MM: the spec has machines or
 // maintainers (their tags, identifiers and dedupe); compiled out otherwise to keep the VGPR budget.
 // One env's render (observation_builder.py:138-235) in its LDS slice.
-template <int MAXPTS, typename OT, bool MM, int PK, bool DIRT, bool MW = false, int R = 0>
+template <int MAXPTS, typename OT, bool MM, int PK, bool DIRT, bool MW = false, int R = 0, bool NARROW = false>
 __device__ __forceinline__ void obs_env(SpecP S, uint8_t* slice, const uint8_t* state, long long env, OT* obs,
                                         ObsPacked pk, int wv = 0, int nwv = 1, int slot = 0) {
   // slice: [lean record][cell map][pairs] (+ per-wave tables, build_obs)
@@ -3732,9 +3778,10 @@ __device__ __forceinline__ void obs_env(SpecP S, uint8_t* slice, const uint8_t* 
     pk.val = pk.val ? pk.val + ea * pk.cap : nullptr;
     pk.cnt = pk.cnt ? pk.cnt + ea : nullptr;
     pk.emb = pk.emb ? pk.emb + ea * pk.E : nullptr;
-    build_obs<MAXPTS, OT, MM, PK, DIRT, MW, R>(e, nullptr, pg, pk, wv, nwv, slot);
+    build_obs<MAXPTS, OT, MM, PK, DIRT, MW, R, NARROW>(e, nullptr, pg, pk, wv, nwv, slot);
   } else {
-    build_obs<MAXPTS, OT, MM, PK, DIRT, MW, R>(e, obs + (size_t)env * S->A * S->obs_agent_stride, pg, pk, wv, nwv, slot);
+    build_obs<MAXPTS, OT, MM, PK, DIRT, MW, R, NARROW>(e, obs + (size_t)env * S->A * S->obs_agent_stride, pg, pk, wv, nwv,
+                                                       slot);
   }
   // k_obs reads only [0, o_mt) of the record and stores only this word: the replay of the same call may run beside it
   // on the engine's second stream and writes H_DEBT / H_MT_IDX (single words) and [o_mt, o_perm + 2 nf) (replay_env)
@@ -3750,7 +3797,7 @@ __device__ __forceinline__ void obs_env(SpecP S, uint8_t* slice, const uint8_t* 
 #ifndef MFG_OBS_GEO_WPE
 #define MFG_OBS_GEO_WPE 7  // waves per SIMD asked for the folded-geometry render
 #endif
-template <int MAXPTS, typename OT, bool MM, int PK, bool DIRT, int R = 0>
+template <int MAXPTS, typename OT, bool MM, int PK, bool DIRT, int R = 0, bool NARROW = false>
 static __global__ void __launch_bounds__(MFG_WPB * 64) __attribute__((amdgpu_waves_per_eu(R > 0 ? MFG_OBS_GEO_WPE : (MAXPTS <= 8 ? 7 : 1)))) k_obs(const MfgDevSpec* S_, const uint8_t* state, long long B,
                                                       OT* obs, ObsPacked pk, const uint8_t* skip) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -3759,7 +3806,7 @@ static __global__ void __launch_bounds__(MFG_WPB * 64) __attribute__((amdgpu_wav
   const long long env = (long long)blockIdx.x * (blockDim.x >> 6) + wid;
   if (env >= B) return;
   if (skip && skip[env]) return;
-  obs_env<MAXPTS, OT, MM, PK, DIRT, false, R>(S, smem + (size_t)wid * S->lds_obs, state, env, obs, pk);
+  obs_env<MAXPTS, OT, MM, PK, DIRT, false, R, NARROW>(S, smem + (size_t)wid * S->lds_obs, state, env, obs, pk);
 }
 // Multi-wave render: one env per workgroup of nwv waves (specs whose per-env render slice is large, C5: a
 // 128 x 128 u16 cell map; the waves share it and split the agents)
@@ -3806,7 +3853,7 @@ static __global__ void __launch_bounds__(MFG_WAVE) k_obs_lr(const MfgDevSpec* S_
   }
 }
 // Render of the envs of a done list (rd_list row: [0] = count, [2..] = envs): a resident grid strides over it.
-template <int MAXPTS, typename OT, bool MM, int PK, bool DIRT, int R = 0>
+template <int MAXPTS, typename OT, bool MM, int PK, bool DIRT, int R = 0, bool NARROW = false>
 static __global__ void __launch_bounds__(MFG_WPB * 64) k_obs_list(const MfgDevSpec* S_, const uint8_t* state, long long B,
                                                            OT* obs, ObsPacked pk, const int32_t* list) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -3817,7 +3864,7 @@ static __global__ void __launch_bounds__(MFG_WPB * 64) k_obs_list(const MfgDevSp
   for (long long q = (long long)blockIdx.x * (blockDim.x >> 6) + wid; q < n; q += nw) {
     const long long env = uni(list[2 + q]);
     if (env >= 0 && env < B)
-      obs_env<MAXPTS, OT, MM, PK, DIRT, false, R>(S, smem + (size_t)wid * S->lds_obs, state, env, obs, pk);
+      obs_env<MAXPTS, OT, MM, PK, DIRT, false, R, NARROW>(S, smem + (size_t)wid * S->lds_obs, state, env, obs, pk);
   }
 }
 
@@ -4128,31 +4175,32 @@ hipError_t launch_obs_inst(const ObsLaunch& L, OT* obs, const ObsPacked& pk, hip
     }                                                                                                            \
   }
 // the single-wave dense render with pomdp_r == R's window geometry folded (k_obs / k_obs_list <2R + 2, OT, MM, 0, DIRT,
-// R>; instantiated in mfg_obs_g.hip). mfg_create decides whether a spec takes it (mfg_engine.obs_geo_r).
-template <int R, typename OT>
+// R, NARROW>; the three-word records instantiated in mfg_obs_g.hip, the one-word ones in mfg_obs_h.hip). mfg_create
+// decides whether a spec takes it (mfg_engine.obs_geo_r, obs_narrow).
+template <int R, typename OT, bool NARROW>
 hipError_t launch_obs_geo(const ObsLaunch& L, OT* obs, hipStream_t st, const uint8_t* skip, const int32_t* list);
 #define MFG_OBS_GEO_LAUNCH_IF(MMV, DV)                                                                           \
   if (L.mm == MMV && L.dirt == DV) {                                                                             \
     if (list)                                                                                                    \
-      hipLaunchKernelGGL((k_obs_list<2 * R + 2, OT, MMV, 0, DV, R>), dim3(L.grid), dim3(L.W * 64), L.lds, st,    \
-                         L.d_spec, L.d_state, L.B, obs, ObsPacked{}, list);                                      \
+      hipLaunchKernelGGL((k_obs_list<2 * R + 2, OT, MMV, 0, DV, R, NARROW>), dim3(L.grid), dim3(L.W * 64), L.lds, \
+                         st, L.d_spec, L.d_state, L.B, obs, ObsPacked{}, list);                                  \
     else                                                                                                         \
-      hipLaunchKernelGGL((k_obs<2 * R + 2, OT, MMV, 0, DV, R>), dim3(L.grid), dim3(L.W * 64), L.lds, st,         \
+      hipLaunchKernelGGL((k_obs<2 * R + 2, OT, MMV, 0, DV, R, NARROW>), dim3(L.grid), dim3(L.W * 64), L.lds, st, \
                          L.d_spec, L.d_state, L.B, obs, ObsPacked{}, skip);                                      \
   }
 #define MFG_DEFINE_LAUNCH_OBS_GEO                                                                                \
-  template <int R, typename OT>                                                                                  \
+  template <int R, typename OT, bool NARROW>                                                                     \
   hipError_t launch_obs_geo(const ObsLaunch& L, OT* obs, hipStream_t st, const uint8_t* skip,                    \
                             const int32_t* list) {                                                               \
     MFG_OBS_GEO_LAUNCH_IF(true, true) else MFG_OBS_GEO_LAUNCH_IF(true, false)                                    \
     else MFG_OBS_GEO_LAUNCH_IF(false, true) else MFG_OBS_GEO_LAUNCH_IF(false, false)                             \
     return hipGetLastError();                                                                                    \
   }
-#define MFG_INSTANTIATE_OBS_GEO(R)                                                                               \
-  template hipError_t launch_obs_geo<R, double>(const ObsLaunch&, double*, hipStream_t, const uint8_t*,          \
-                                                const int32_t*);                                                 \
-  template hipError_t launch_obs_geo<R, float>(const ObsLaunch&, float*, hipStream_t, const uint8_t*,            \
-                                               const int32_t*);
+#define MFG_INSTANTIATE_OBS_GEO(R, NARROW)                                                                       \
+  template hipError_t launch_obs_geo<R, double, NARROW>(const ObsLaunch&, double*, hipStream_t, const uint8_t*,  \
+                                                        const int32_t*);                                         \
+  template hipError_t launch_obs_geo<R, float, NARROW>(const ObsLaunch&, float*, hipStream_t, const uint8_t*,    \
+                                                       const int32_t*);
 // explicit instantiations of one ray length (the obs modes: packed + fused projection, packed entries only, f64, f32)
 #define MFG_INSTANTIATE_OBS(MP)                                                                                  \
   template hipError_t launch_obs_inst<MP, float, 2>(const ObsLaunch&, float*, const ObsPacked&, hipStream_t,      \

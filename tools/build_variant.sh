@@ -7,7 +7,9 @@
 #   UNITS=mfg_engine  a variant of the host unit only (k_logic, k_replay*, resets) reuses the render objects;
 #   UNITS=mfg_obs_a   a render variant: mfg_obs_a holds ray lengths 4-8 (C2/C3), mfg_obs_b C4's 10-point rays,
 #                     mfg_obs_c C5's 18; mfg_obs_g the dense renders with pomdp_r 1-3's window geometry folded
-#                     (C2/C3 dense obs run these: -DMFG_OBS_GEO_ALIGN=0, -DMFG_OBS_GEO_LANE_OPAQUE=0, -DMFG_OBS_GEO_WPE=8).
+#                     (-DMFG_OBS_GEO_ALIGN=0, -DMFG_OBS_GEO_LANE_OPAQUE=0, -DMFG_OBS_GEO_WPE=8), mfg_obs_h the same with
+#                     one-word records (C2/C3 dense obs run these; wider specs run mfg_obs_g's).
+#   UNITS="mfg_engine mfg_obs_h" with -DMFG_OBS_NARROW=0: C2/C3 back on mfg_obs_g's three-word records.
 # One variant at a time: each build is already one compile per unit in parallel.
 set -e
 cd "$(dirname "$0")/.."
