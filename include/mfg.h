@@ -292,6 +292,10 @@ typedef struct mfg_variant {
                                  spec at run time) instead of the one compiled for that radius: parity and A/B runs */
   int32_t obs_wide_records;   /* 1: the folded render of specs with at most 16 agents keeps the three-word cell and layer
                                  records (the ones of wider specs) instead of the one-word ones: parity runs */
+  int32_t obs_waves;          /* 1, 2, 4 or 8: that many render waves per env (1: the single-wave render k_obs, more: the
+                                 multi-wave render k_obs_mw) under mfg_create's own conditions: more than one wave needs
+                                 observation rays of 10 to 64 points, and the workgroup's LDS must fit a CU. A value that
+                                 cannot be honoured makes mfg_create_variant fail with a message. */
 } mfg_variant;
 int mfg_create_variant(const mfg_spec* spec, int device, int64_t n_envs, const mfg_variant* variant,
                        mfg_engine** out);
@@ -338,7 +342,9 @@ int mfg_replay(mfg_engine* e, void* stream);
 
 /* Per-env state record layout (offsets) for host-side decoding, then the engine's launch facts (LDS slices,
  * o_logic, reset_overlap: 1 when a step's resets and their render run on the engine's second stream beside the
- * render of the other envs); returns the number of ints written (<= 64). */
+ * render of the other envs, obs_geo_r, obs_narrow, and last the render's shape: obs_maxpts, the ray length (MAXPTS)
+ * the render kernels are instantiated for, 0 = the long-ray render; obs_waves, the render waves per env actually
+ * used, 1 for the single-wave and the long-ray render); returns the number of ints written (<= 64). */
 int mfg_layout(const mfg_engine* e, int32_t* out);
 void* mfg_state_ptr(mfg_engine* e);
 int64_t mfg_state_bytes(const mfg_engine* e);

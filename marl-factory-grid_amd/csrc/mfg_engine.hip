@@ -333,7 +333,7 @@ extern "C" int mfg_create_variant(const mfg_spec* s, int device, int64_t n_envs,
   if (!s || !out) return fail("null argument");
   if (n_envs < 1) return fail("n_envs must be >= 1");
   if (validate_spec(s)) return -1;
-  const mfg_variant none{0, 0, 0, 0, 0, 0, 0, 0};
+  const mfg_variant none{0, 0, 0, 0, 0, 0, 0, 0, 0};
   DevGuard g(device);
   return create_impl(s, device, n_envs, v ? *v : none, out);
 }
@@ -780,6 +780,20 @@ static int create_impl(const mfg_spec* s, int device, int64_t n_envs, const mfg_
           const size_t wg = (size_t)h.lds_obs_shared + (size_t)nwv * h.lds_obs_wave;
           if (wg <= MFG_LDS_MAX && waves_per_cu(nwv) > best) { best = waves_per_cu(nwv); e->obs_nwv = nwv; }
         }
+      if (v.obs_waves) {  // mfg_variant (tests): that many waves, under the same conditions
+        const int nwv = v.obs_waves;
+        if (nwv != 1 && nwv != 2 && nwv != 4 && nwv != 8) {
+          delete e; return fail("mfg_variant.obs_waves must be 0, 1, 2, 4 or 8");
+        }
+        if (nwv > 1 && h.maxpts < 10) {
+          delete e; return fail("mfg_variant.obs_waves > 1 needs observation rays of 10 to 64 points (the multi-wave render)");
+        }
+        const size_t wg = nwv == 1 ? (size_t)h.lds_obs : (size_t)h.lds_obs_shared + (size_t)nwv * h.lds_obs_wave;
+        if (wg > MFG_LDS_MAX) {
+          delete e; return fail("mfg_variant.obs_waves: the render workgroup's LDS does not fit a CU");
+        }
+        e->obs_nwv = nwv;
+      }
     }
     const int ow = std::min(MFG_WPB, wpb_for(h.lds_obs));
     const int obs_per_cu = std::max(1, std::min(32 / ow, (int)(MFG_LDS_MAX / ((size_t)h.lds_obs * ow))));
@@ -823,7 +837,8 @@ extern "C" int mfg_destroy(mfg_engine* e) {
 // [size, o_hdr, ..., o_perm, lmax, obs_agent_stride, lds_full, xchg_ordered, o_machines, ..., scratch_bytes, o_logic,
 //  reset_overlap (1: with auto-reset and obs, a step's resets and their render run on the engine's second stream),
 //  obs_geo_r (> 0: dense obs are rendered by the kernels with this pomdp_r's window geometry folded, 0: the generic ones),
-//  obs_narrow (1: the folded render with one-word cell and layer records)]
+//  obs_narrow (1: the folded render with one-word cell and layer records),
+//  obs_maxpts (the MAXPTS the render is instantiated for, 0: the long-ray render), obs_waves (render waves per env)]
 extern "C" int mfg_layout(const mfg_engine* e, int32_t* out) {
   const MfgLayout& L = e->h.L;
   const int32_t v[] = {L.size, L.o_hdr, L.o_rule_ctr, L.o_agent_pos, L.o_agent_arr, L.o_agent_par, L.o_frozen_org,
@@ -832,7 +847,8 @@ extern "C" int mfg_layout(const mfg_engine* e, int32_t* out) {
                        e->h.lmax, e->h.obs_agent_stride, e->h.lds_full, e->h.xchg_ordered, L.o_machines,
                        L.o_maints, L.o_mstate, L.o_mpath, L.o_grank, e->h.dirt_cap, e->h.lds_logic, e->h.lds_obs,
                        e->h.lds_replay_per_wave, e->h.bfs_off, e->h.bfs_bytes, e->h.max_pairs, e->h.scratch_bytes,
-                       L.o_logic, e->overlap ? 1 : 0, e->obs_geo_r, e->obs_narrow};
+                       L.o_logic, e->overlap ? 1 : 0, e->obs_geo_r, e->obs_narrow, e->maxpts,
+                       e->maxpts ? e->obs_nwv : 1};
   const int n = (int)(sizeof(v) / sizeof(v[0]));
   for (int i = 0; i < n; i++) out[i] = v[i];
   return n;

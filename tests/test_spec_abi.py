@@ -206,6 +206,10 @@ def test_struct_layouts_agree():
     assert C.sizeof(O.Res) == L.oracle_sizeof_res()
     L.oracle_sizeof_packed_obs.restype = C.c_int
     assert C.sizeof(abi.MfgPackedObs) == L.oracle_sizeof_packed_obs()
+    from mfg_amd.engine import MfgVariant
+    L.oracle_sizeof_variant.restype = C.c_int
+    assert C.sizeof(MfgVariant) == L.oracle_sizeof_variant()
+    assert [f for f, _ in MfgVariant._fields_][-1] == 'obs_waves'
 
 
 def test_philox_known_answer():
