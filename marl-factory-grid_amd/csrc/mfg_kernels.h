@@ -396,6 +396,12 @@ static_assert(H_DEBT < RP_HDR_N && H_MT_IDX < RP_HDR_N, "k_replay header slice")
 #ifndef RP_SERIAL_FWD
 #define RP_SERIAL_FWD 4  // blocks with at most this many forwards resolve them serially (no LDS table)
 #endif
+#ifndef MFG_RP_TAIL
+// replay_shuffle_t: chunks at icur <= this take per-lane widths (0: none, the one-width schedule throughout). Any
+// value from 80 to 126 gives C3 the same schedule: the band 63..126 starts with one full one-width chunk (about 48
+// ranks), the tail takes the rest of the shuffle in 2 chunks.
+#define MFG_RP_TAIL 95
+#endif
 // The chunk's acceptance fixed point: from the seed m, iterate m = ballot(mbcnt(m) <= c) until it is stable;
 // returns A = mbcnt(m) (#accepted lanes below this one) and leaves the accepted set in m.
 __device__ __forceinline__ int accept_ranks(u64& m, int c) {
@@ -432,7 +438,9 @@ __device__ int replay_shuffle_t(const Env& e, uint16_t* perm, int hi) {
   // words are already in yw follows from idx alone (a twisted state had idx >= 624 > 560).
   uint32_t yw = idx <= 560 ? mt[idx + lane] : 0u;
   const int lane34 = (3 * lane) >> 2;
-  while (icur >= lo) {
+  // One chunk of 64 words, shared by the two loops below. MIXED: per-lane widths (the tail), else one width.
+  auto chunk = [&](auto mixed) {
+    constexpr bool MIXED = decltype(mixed)::value;
     if (idx > 560) {
       if (idx >= 624) {
         mt_twist(e);
@@ -451,21 +459,49 @@ __device__ int replay_shuffle_t(const Env& e, uint16_t* perm, int hi) {
     // One bit width per chunk: k = bitlen(icur + 1), and the chunk stops where bitlen(i + 1) would
     // change (i < 2^(k-1) - 1) or at lo. Within it accept <=> A <= c = min(icur - r, span), with
     // r = y >> (32 - k) fixed per lane, and lanes whose A exceeds span are not consumed (their words
-    // start the next chunk). So every chunk takes the same branch-free path, power-of-two crossings
-    // and the i < 64 tail included.
+    // start the next chunk). So every chunk of the main loop takes the same branch-free path, power-of-two
+    // crossings included.
+    uint32_t r;
+    u64 m;
+    int A, nacc, consumed;
+    if constexpr (!MIXED) {
     const int sh = __clz(icur + 1);
     const int span = icur - max(lo, (int)(0x80000000u >> sh) - 1);  // highest rank at width k
-    uint32_t r = y >> sh;
+    r = y >> sh;
     const int c = min(icur - (int)r, span);
     // A_l = #accepted lanes < l: Jacobi iteration from a seed at A_l ~ 3l/4 (the mean acceptance; 1.91 rounds per
     // chunk instead of 2.15 from the sure lower bound c_l >= l, simulated over C3's chunks). Any seed converges to
     // the same unique fixed point (lane l is exact after l rounds).
-    u64 m = ballot(c >= lane34);
-    const int A = accept_ranks(m, c);
-    const int nacc = popc(m);
+    m = ballot(c >= lane34);
+    A = accept_ranks(m, c);
+    nacc = popc(m);
     // ranks are monotone in the lane: all 64 words are consumed unless the band fills (nacc = span + 1), and then
     // exactly the lanes up to the last accepted one (scalar, no vector compare)
-    const int consumed = nacc > span ? 64 - __builtin_clzll(m) : 64;
+    consumed = nacc > span ? 64 - __builtin_clzll(m) : 64;
+    } else {
+    // The tail (icur <= MFG_RP_TAIL): the width bands below 2^k are 2^(k-1) ranks wide, a chunk each for a handful
+    // of draws. Here every lane takes the width of its own rank instead, i = icur - A and r = y >> clz(i + 1), and
+    // accepts <=> i >= lo && r <= i, so a chunk stops only where the shuffle ends. Lane l still depends on the
+    // lanes below it alone: the same Jacobi iteration from the seed at A ~ 3l/4, with the draw re-read at the new
+    // rank in every round (about 5 rounds instead of 2, in the 2 tail chunks of a shuffle; tools/replay_census.py).
+    // Lanes past the shuffle's end have i < lo: their shift count and r are unused (shifts read the low 5 bits).
+    auto draws = [&](int a) {
+      const int i = icur - a;
+      r = y >> (__clz(i + 1) & 31);
+      return ballot(i >= lo && (int)r <= i);
+    };
+    m = draws(lane34);
+    for (;;) {
+      A = mbcnt(m);
+      const u64 m2 = draws(A);
+      if (m2 == m) break;
+      m = m2;
+    }
+    nacc = popc(m);
+    // all 64 words are consumed unless the shuffle ends here (every rank icur .. lo drawn): then the lanes up to
+    // the last accepted one, and the words after it start the next shuffle
+    consumed = nacc > icur - lo ? 64 - __builtin_clzll(m) : 64;
+    }
     const int inext = icur - nacc, idxn = idx + consumed;
     if constexpr (!SWAP) {
       if (first_j < 0 && m) first_j = rl((int)r, ffs64(m));
@@ -529,6 +565,12 @@ __device__ int replay_shuffle_t(const Env& e, uint16_t* perm, int hi) {
     }
     icur = inext;
     idx = idxn;
+  };
+  // The main loop leaves the tail to the mixed chunks (it ends inside its last band, at or below MFG_RP_TAIL).
+  static_assert(MFG_RP_TAIL >= 0, "the main loop's exit bound keeps icur >= lo");
+  while (icur > MFG_RP_TAIL) chunk(std::false_type{});
+  if constexpr (MFG_RP_TAIL > 0) {
+    while (icur >= lo) chunk(std::true_type{});
   }
   if (idx > 624) {  // words of the next state were consumed: make the state canonical (CPython's mti)
     mt_twist(e);
