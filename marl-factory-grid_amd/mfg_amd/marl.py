@@ -32,6 +32,7 @@ import torch.nn.functional as F
 from torch.distributions import Categorical
 
 from . import gru_window, learn_lib
+from .rollout import Rollout, WindowRollout, _project_dense, graph_run  # noqa: F401 (_project_dense: the tools' name)
 
 # the names of the former per-unit binders: callers written against them get the one binding
 _gru_lib = _ppo_lib = learn_lib.lib
@@ -294,21 +295,6 @@ def _packed_weight_grad(idx, val, g, k):
     return gw
 
 
-def _project_dense(idx, val, proj):
-    """obs_proj over packed rows without grad: the rows scattered to dense blocks (<= 512 MiB) and one GEMM each
-    (embedding_bag with per-sample weights ran 0.77 ms for C3's 65,536 rows on the MI355X)."""
-    lead, cap = idx.shape[:-1], idx.shape[-1]
-    idx2, val2 = idx.reshape(-1, cap).long(), val.reshape(-1, cap)
-    k = proj.weight.shape[1]
-    out = torch.empty((idx2.shape[0], proj.weight.shape[0]), dtype=proj.weight.dtype, device=idx2.device)
-    step = max(1, (1 << 27) // max(k, 1))
-    for r0 in range(0, idx2.shape[0], step):
-        d = torch.zeros((min(step, idx2.shape[0] - r0), k), dtype=proj.weight.dtype, device=idx2.device)
-        d.scatter_add_(1, idx2[r0:r0 + step], val2[r0:r0 + step].to(d.dtype))
-        torch.addmm(proj.bias, d, proj.weight.t(), out=out[r0:r0 + step])
-    return out.view(*lead, -1)
-
-
 class _EngineProj(torch.autograd.Function):
     """obs_proj(obs) for the learner, forward taken from the engine: every slot of the window was rendered with
     the current weights (the fused projection of k_obs, MFG_OBS_PACKED), so the forward is that output (bias
@@ -508,7 +494,15 @@ def a2c_loss_terms(logits, critic, actions, reward, done, gamma, entropy_coef, v
     return loss.mean()
 
 
-class BatchedA2C:
+def _one_action_count(spec, name):
+    """The action count all agents of spec share (the learners with one shared network refuse any other team)."""
+    n_act = set(int(x) for x in spec.n_actions)
+    if len(n_act) != 1:
+        raise ValueError(f'{name} shares one network: all agents need the same number of actions')
+    return n_act.pop()
+
+
+class BatchedA2C(WindowRollout):
     """A2C with a shared ``RecurrentAC`` over B envs x A agents of one engine, everything on the device.
 
     Per step: the engine renders o_t as packed rows + the fused ``obs_proj`` (one kernel, no dense obs); the
@@ -540,26 +534,10 @@ class BatchedA2C:
     def __init__(self, factory, net=None, n_steps=5, gamma=0.99, entropy_coef=0.01, vf_coef=0.5, gae_coef=0.0,
                  lr=3e-4, cap=32, obs_emb_size=96, action_emb_size=16, hidden_size=64, use_agent_embedding=False,
                  check_cap=True, generator=None, engine_emb=True, graph=False, act_graph=False, reuse_acting=True):
-        from .engine import PackedObs
-        self.f = factory
-        eng = factory.engine
-        spec = factory.spec
-        self.B, self.A = eng.B, eng.A
-        self.N = self.B * self.A
-        self.dev = eng.device
-        n_act = set(int(x) for x in spec.n_actions)
-        if len(n_act) != 1:
-            raise ValueError('BatchedA2C shares one network: all agents need the same number of actions')
-        self.n_actions = n_act.pop()
-        kdim = eng.lmax * eng.obs_hw[0] * eng.obs_hw[1]
-        if not check_cap and cap < kdim:
-            # a truncated row would make acting (the fused emb sums every nonzero entry) and learning (the stored
-            # cap entries only) see different obs_proj inputs: skipping the check is allowed only when no row
-            # can be truncated
-            raise ValueError(f'check_cap=False needs cap >= lmax*h*w = {kdim} (rows can hold up to that many '
-                             f'nonzero entries); got cap {cap}')
+        self.n_actions = _one_action_count(factory.spec, 'BatchedA2C')
+        super().__init__(factory, cap, check_cap, generator)
         self.net = net if net is not None else RecurrentAC(
-            kdim, self.n_actions, obs_emb_size, action_emb_size, hidden_size, hidden_size, self.A,
+            self.kdim, self.n_actions, obs_emb_size, action_emb_size, hidden_size, hidden_size, self.A,
             use_agent_embedding=use_agent_embedding)
         self.net.to(self.dev)
         self.graph = bool(graph)
@@ -571,21 +549,11 @@ class BatchedA2C:
         self._graph, self._warm = None, 0
         self.T, self.gamma, self.entropy_coef, self.vf_coef, self.gae_coef = n_steps, gamma, entropy_coef, \
             vf_coef, gae_coef
-        self.check_cap = check_cap
         self.engine_emb = engine_emb  # learner forward of obs_proj: the engine's fused output (True) or a gather
-        self.gen = generator
         T, N, dev = self.T, self.N, self.dev
-        # obs slots o_0..o_T of the window (entries + fused projection), written by the engine
-        self.pobs = PackedObs(eng, K=T + 1, cap=cap, weight=self.net.obs_proj.weight, bias=self.net.obs_proj.bias)
-        self.slot = [self.pobs.view(k) for k in range(T + 1)]
-        self.act_in = torch.full((T + 1, self.B, self.A), -1, dtype=torch.int64, device=dev)  # a_{t-1}, -1 = none
-        self.act = torch.zeros((T, self.B, self.A), dtype=torch.int32, device=dev)
-        self.rew = torch.zeros((T, self.B, self.A), dtype=torch.float64, device=dev)
-        self.done = torch.zeros((T, self.B), dtype=torch.uint8, device=dev)
         H = self.net.hidden_size_actor
-        self.h0a = torch.zeros((N, 1, H), device=dev)  # hidden state fed at entry 0 of the window
-        self.h0c = torch.zeros((N, 1, self.net.hidden_size_critic), device=dev)
-        self.ha, self.hc = self.h0a.clone(), self.h0c.clone()  # persistent: updated in place (graph inputs)
+        # obs slots o_0..o_T of the window (entries + fused projection); h0a / h0c: the states fed at its entry 0
+        self._alloc((H, self.net.hidden_size_critic), proj=self.net.obs_proj)
         self._ha_new, self._hc_new = self.h0a.clone(), self.h0c.clone()  # the policy step's new states (static)
         # reuse_acting: the acting steps run both GRUs through mfg_gru_fwd_step and keep every entry's outputs and
         # gate activations (the weights are fixed over a window, so they ARE the learner's recurrent forward of
@@ -609,17 +577,6 @@ class BatchedA2C:
         self._u = torch.empty(N, device=dev)  # the sampling uniforms (static: graph-captured acting)
         self.last_loss = torch.zeros((), device=dev)
         self.agent_ids = torch.arange(self.A, device=dev).repeat(self.B)
-        self.t = 0
-        self.updates = 0
-        self.episodes = torch.zeros((), dtype=torch.float64, device=dev)  # finished episodes, counted per window
-        self.reward_sum = torch.zeros((), dtype=torch.float64, device=dev)
-        self._started = False
-
-    def reset(self):
-        self.f.engine.reset(obs=self.slot[0], init=0 if self.f._created else 1, seed_base=self.f.seed_base)
-        self.f._created = True
-        self._started = True
-        self.t = 0
 
     @torch.no_grad()
     def step(self):
@@ -628,21 +585,10 @@ class BatchedA2C:
             self.reset()
         t = self.t
         self._policy_step(t)
-        # the shuffle-debt replay once per window, at its last step (MFG_STEP_DEFER_REPLAY)
-        self.f.engine.step(1, actions=self.act[t], reward=self.rew[t], done=self.done[t], obs=self.slot[t + 1],
-                           auto_reset=True, step_base=self.f.t, defer_replay=t + 1 < self.T)
-        self.f.t += 1
-        d = self.done[t].bool()
-        # the next entry's inputs: last action (-1 after an episode end) and the recurrent state (zero then)
-        a = self.act[t].long()
-        self.act_in[t + 1].copy_(torch.where(d.view(-1, 1), torch.full_like(a, -1), a))
-        keep = (~d).to(self.ha.dtype).view(self.B, 1, 1)  # broadcast over the env's agents
-        ha_new, hc_new = (self.hs_a[t], self.hs_c[t]) if self.reuse else (self._ha_new, self._hc_new)
-        torch.mul(ha_new.view(self.B, self.A, -1), keep, out=self.ha.view(self.B, self.A, -1))
-        torch.mul(hc_new.view(self.B, self.A, -1), keep, out=self.hc.view(self.B, self.A, -1))
-        self.t += 1
-        if self.t == self.T:
-            self.learn()
+        if self.reuse:
+            self._window_step(self.hs_a[t], self.hs_c[t])
+        else:
+            self._window_step(self._ha_new, self._hc_new)
 
     @torch.no_grad()
     def _policy(self, t):
@@ -700,24 +646,10 @@ class BatchedA2C:
     def _policy_step(self, t):
         if not self.act_graph:
             return self._policy(t)
-        g = self._act_graphs.get(t)
+        g, self._act_warm[t] = graph_run(self.dev, lambda: self._policy(t), self._act_graphs.get(t),
+                                         self._act_warm.get(t, 0))
         if g is not None:
-            g.replay()
-            return
-        cur = torch.cuda.current_stream(self.dev)
-        if self._act_warm.get(t, 0) < 2:  # eager warm-up on a side stream (lazy library state outside the capture)
-            side = torch.cuda.Stream(self.dev)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                self._policy(t)
-            cur.wait_stream(side)
-            self._act_warm[t] = self._act_warm.get(t, 0) + 1
-            return
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._policy(t)
-        self._act_graphs[t] = g
-        g.replay()  # capture records only: this step's policy runs here
+            self._act_graphs[t] = g
 
     def window(self):
         """The window's learner inputs: packed entries [N, T+1, cap], action inputs [N, T+1], starts,
@@ -793,32 +725,13 @@ class BatchedA2C:
 
     def learn(self):
         """One A2C update on the window (base_ac.py:200-225), then slide: o_T becomes o_0."""
-        if self.check_cap:
-            self.pobs.check()
-            if self.gen is None and self.dev.type == 'cuda' and bool((self.act < 0).any()):
-                # mfg_sample_categorical marks rows with non-finite logits -1 (the engine took them as crash actions)
-                raise RuntimeError('BatchedA2C: non-finite policy logits in this window (training diverged)')
-        # episode and reward counters once per window (two reductions instead of two per step)
-        self.episodes += self.done.sum()
-        self.reward_sum += self.rew.sum()
+        self._check('BatchedA2C', 'in this window')
+        self._fold()
         if not self.graph:
             self._update()
-        elif self._graph is not None:
-            self._graph.replay()
-        elif self._warm < 2:  # eager warm-up on a side stream (lazy library state outside the capture)
-            side = torch.cuda.Stream(self.dev)
-            side.wait_stream(torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(side):
-                self._update()
-            torch.cuda.current_stream(self.dev).wait_stream(side)
-            self._warm += 1
-        else:
-            g = torch.cuda.CUDAGraph()
-            self.opt.zero_grad(set_to_none=True)
-            with torch.cuda.graph(g):
-                self._update()
-            self._graph = g
-            g.replay()  # capture records only: this update runs here
+        else:  # (the gradients are dropped before the capture begins, not inside it)
+            self._graph, self._warm = graph_run(self.dev, self._update, self._graph, self._warm,
+                                                lambda: self.opt.zero_grad(set_to_none=True))
         self.updates += 1
         self.t = 0
 
@@ -832,32 +745,8 @@ class BatchedA2C:
             self.opt.step()
         with torch.no_grad():
             self.last_loss.copy_(loss.detach())
-            T = self.T
-            self.pobs.idx[0].copy_(self.pobs.idx[T])
-            self.pobs.val[0].copy_(self.pobs.val[T])
-            self.pobs.count[0].copy_(self.pobs.count[T])
-            self.act_in[0].copy_(self.act_in[T])
-            self.h0a.copy_(self.ha)
-            self.h0c.copy_(self.hc)
-            # new weights: the engine projects with them from now on; o_0's projection is redone here
-            self.pobs.set_projection(self.net.obs_proj.weight, self.net.obs_proj.bias)
-            self._project_slot0()
-
-    def _project_slot0(self):
-        """o_0's fused projection redone with the new weights (the engine rendered it with the old ones): one
-        mfg_packed_project over its packed rows on the GPU."""
-        pb = self.pobs
-        if not pb.idx.is_cuda:
-            pb.emb[0].copy_(_project_dense(pb.idx[0], pb.val[0], self.net.obs_proj))
-            return
-        learn_lib.call('mfg_packed_project', pb.idx[0].data_ptr(), pb.val[0].data_ptr(), self.N, pb.cap,
-                       pb.wt.data_ptr(), pb.bias.data_ptr(), pb.E, pb.kdim, pb.emb[0].data_ptr(), pb.E,
-                       learn_lib.stream(self.dev))
-
-    def train(self, n_updates):
-        for _ in range(n_updates * self.T):
-            self.step()
-        return self.last_loss
+            self._slide()
+            self.project_slot(0)  # new weights: the engine projects with them from now on; o_0's projection is redone
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -991,17 +880,17 @@ def _draw_uniform(mask, u):
     return torch.searchsorted(c, k).squeeze(1)
 
 
-class BatchedMAPPO:
+class BatchedMAPPO(Rollout):
     """MAPPO (``algorithms/marl/mappo.py`` ``LoopMAPPO``) with a shared ``RecurrentAC`` over B envs x A agents of one
     engine, everything on the device: a clipped PPO surrogate on normalised Monte-Carlo returns, a replay buffer of
     ``buffer_size`` steps, ``n_updates`` minibatches of ``batch_size`` chunks of ``n_steps`` steps per learn call,
     Adam(lr 3e-4, eps 1e-5) and ``clip_grad_norm_(0.5)`` (``mappo.py:14-28``).
 
-    Acting is ``BatchedA2C``'s (without the stored-activation reuse): the engine renders o_t as packed rows + the
-    fused ``obs_proj``, the policy acts on (o_t, a_{t-1}, h_t) through ``forward_emb``, ``_sample`` draws the action,
-    the engine steps with ``auto_reset``; after a done the next entry's action input is -1 and its recurrent state
-    zero. The memory is aligned as in ``BatchedA2C``: entry t holds (o_t, a_{t-1}) as the network input and a_t, r_t,
-    d_t as targets.
+    Acting runs on the shared rollout core (``rollout.Rollout``) with ``BatchedA2C``'s policy step, without the
+    stored-activation reuse: the engine renders o_t as packed rows + the fused ``obs_proj``, the policy acts on (o_t,
+    a_{t-1}, h_t) through ``forward_emb``, ``_sample`` draws the action, the engine steps with ``auto_reset`` (its replay
+    never deferred); after a done the next entry's action input is -1 and its recurrent state zero. The memory is
+    aligned as in ``BatchedA2C``: entry t holds (o_t, a_{t-1}) as the network input and a_t, r_t, d_t as targets.
 
     The buffer is a ring of ``buffer_size + 1`` slots on the device: ``buffer_size`` complete entries (a FIFO, as
     the reference's memory with ``reset_memory_after_epoch = False``) and the pending one at the write head, whose
@@ -1019,7 +908,7 @@ class BatchedMAPPO:
     states without restarts (entries 0..T-1 only: entry T is dead in this loss), the loss head (``_PPOHead``: one HIP
     pass for loss and gradients on the GPU with ``fused_head``; ``mappo_loss_terms`` otherwise and on the CPU),
     gradient clipping and Adam. After a learn call the engine's projection weights are refreshed and the pending
-    observation re-projected, as ``BatchedA2C._update`` does.
+    observation re-projected (``project_slot``), as after ``BatchedA2C``'s update.
 
     ``episodes`` / ``reward_sum`` fold in the last ``n_steps`` entries at every learn call, ``updates`` counts
     minibatch updates, ``skipped_updates`` the minibatches skipped because no row had a valid start. With
@@ -1032,58 +921,35 @@ class BatchedMAPPO:
                  entropy_coef=0.01, vf_coef=0.5, clip_range=0.2, lr=3e-4, cap=32, obs_emb_size=96, action_emb_size=16,
                  hidden_size=64, use_agent_embedding=False, chunk_rule='episode', fused_head=True, check_cap=True,
                  generator=None):
-        from .engine import PackedObs
-        self.f = factory
-        eng = factory.engine
-        self.B, self.A = eng.B, eng.A
-        self.N = self.B * self.A
-        self.dev = eng.device
-        n_act = set(int(x) for x in factory.spec.n_actions)
-        if len(n_act) != 1:
-            raise ValueError('BatchedMAPPO shares one network: all agents need the same number of actions')
-        self.n_actions = n_act.pop()
+        self.n_actions = _one_action_count(factory.spec, 'BatchedMAPPO')
         if buffer_size < n_steps + 1:
             raise ValueError(f'buffer_size {buffer_size} holds no chunk start: it must be at least n_steps + 1 = '
                              f'{n_steps + 1}')
         if chunk_rule not in ('episode', 'reference'):
             raise ValueError("chunk_rule must be 'episode' or 'reference'")
-        kdim = eng.lmax * eng.obs_hw[0] * eng.obs_hw[1]
-        if not check_cap and cap < kdim:
-            raise ValueError(f'check_cap=False needs cap >= lmax*h*w = {kdim} (rows can hold up to that many '
-                             f'nonzero entries); got cap {cap}')
+        super().__init__(factory, cap, check_cap, generator)
         self.net = net if net is not None else RecurrentAC(
-            kdim, self.n_actions, obs_emb_size, action_emb_size, hidden_size, hidden_size, self.A,
+            self.kdim, self.n_actions, obs_emb_size, action_emb_size, hidden_size, hidden_size, self.A,
             use_agent_embedding=use_agent_embedding)
         self.net.to(self.dev)
         self.opt = torch.optim.Adam(self.net.parameters(), lr=lr, eps=1e-5)  # mappo.py:16
         self.T, self.S, self.batch_size, self.n_updates = n_steps, buffer_size, batch_size, n_updates
         self.gamma, self.entropy_coef, self.vf_coef, self.clip_range = gamma, entropy_coef, vf_coef, clip_range
-        self.chunk_rule, self.check_cap, self.gen = chunk_rule, check_cap, generator
-        self.fused_head = bool(fused_head)
+        self.chunk_rule, self.fused_head = chunk_rule, bool(fused_head)
         R, N, dev = buffer_size + 1, self.N, self.dev
         self.R = R
-        self.pobs = PackedObs(eng, K=R, cap=cap, weight=self.net.obs_proj.weight, bias=self.net.obs_proj.bias)
-        self.slot = [self.pobs.view(k) for k in range(R)]
-        self.act_in = torch.full((R, self.B, self.A), -1, dtype=torch.int64, device=dev)  # a_{t-1}, -1 = none
-        self.act = torch.zeros((R, self.B, self.A), dtype=torch.int32, device=dev)
-        self.rew = torch.zeros((R, self.B, self.A), dtype=torch.float64, device=dev)
-        self.done = torch.zeros((R, self.B), dtype=torch.uint8, device=dev)
+        # the ring: every slot holds an obs and its targets (the pending entry's are not known yet)
+        self._alloc(R, R, (self.net.hidden_size_actor, self.net.hidden_size_critic), proj=self.net.obs_proj)
         self.logits = torch.zeros((R, N, self.n_actions), device=dev)  # the acting logits (the loss's old policy)
         self.ha_in = torch.zeros((R, N, self.net.hidden_size_actor), device=dev)  # recurrent states fed at the entry
         self.hc_in = torch.zeros((R, N, self.net.hidden_size_critic), device=dev)
-        self.ha = torch.zeros((N, 1, self.net.hidden_size_actor), device=dev)
-        self.hc = torch.zeros((N, 1, self.net.hidden_size_critic), device=dev)
         self._u = torch.empty(N, device=dev)
         self.agent_ids = torch.arange(self.A, device=dev).repeat(self.B)
         self.last_loss = torch.zeros((), device=dev)
         self.head = 0  # the ring slot of the pending entry
         self.filled = 0  # complete entries, at most S
         self.steps = 0
-        self.updates = 0
         self.skipped_updates = 0
-        self.episodes = torch.zeros((), dtype=torch.float64, device=dev)
-        self.reward_sum = torch.zeros((), dtype=torch.float64, device=dev)
-        self._started = False
 
     def buffer_bytes(self):
         """Device bytes of the ring (all R = buffer_size + 1 slots)."""
@@ -1092,9 +958,9 @@ class BatchedMAPPO:
         return sum(b.numel() * b.element_size() for b in bufs)
 
     def reset(self):
-        self.f.engine.reset(obs=self.slot[self.head], init=0 if self.f._created else 1, seed_base=self.f.seed_base)
-        self.f._created = True
-        self._started = True
+        """The shared reset into the pending slot, and what that leaves as it was: the pending entry starts an episode
+        in every env."""
+        super().reset(self.head)
         self.act_in[self.head].fill_(-1)
         self.ha.zero_()
         self.hc.zero_()
@@ -1113,15 +979,8 @@ class BatchedMAPPO:
                                    self.hc, agent_ids=self.agent_ids)
         self.logits[h].copy_(out['logits'][:, 0])
         self._sample(self.logits[h], h)
-        self.f.engine.step(1, actions=self.act[h], reward=self.rew[h], done=self.done[h], obs=self.slot[nxt],
-                           auto_reset=True, step_base=self.f.t)
-        self.f.t += 1
-        d = self.done[h].bool()
-        a = self.act[h].long()
-        self.act_in[nxt].copy_(torch.where(d.view(-1, 1), torch.full_like(a, -1), a))
-        keep = (~d).to(self.ha.dtype).view(self.B, 1, 1)  # broadcast over the env's agents
-        torch.mul(out['hidden_actor'].view(self.B, self.A, -1), keep, out=self.ha.view(self.B, self.A, -1))
-        torch.mul(out['hidden_critic'].view(self.B, self.A, -1), keep, out=self.hc.view(self.B, self.A, -1))
+        # (no deferred replay: the ring has no window whose last step would run it)
+        self._carry(self._env_step(h, nxt, defer_replay=False), out['hidden_actor'], out['hidden_critic'])
         self.head = nxt
         self.filled = min(self.filled + 1, self.S)
         self.steps += 1
@@ -1184,24 +1043,17 @@ class BatchedMAPPO:
         """n_updates minibatch updates once the buffer is full (mappo.py:18-28), then the engine's projection
         weights are refreshed."""
         last = (self.head - 1 - torch.arange(min(self.T, self.filled), device=self.dev)) % self.R
-        self.episodes += self.done[last].sum()
-        self.reward_sum += self.rew[last].sum()
+        self._fold(last)
         if self.filled < self.S:
             return
-        if self.check_cap:
-            self.pobs.check()
-            if self.gen is None and self.dev.type == 'cuda' and bool((self.act < 0).any()):
-                raise RuntimeError('BatchedMAPPO: non-finite policy logits while acting (training diverged)')
+        self._check('BatchedMAPPO', 'while acting')
         for _ in range(self.n_updates):
             picked = self.sample()
             if picked is None:
                 self.skipped_updates += 1
                 continue
             self._update(self.minibatch(*picked))
-        with torch.no_grad():
-            # new weights: the engine projects with them from now on; the pending observation's projection is redone
-            self.pobs.set_projection(self.net.obs_proj.weight, self.net.obs_proj.bias)
-            self._project_slot(self.head)
+        self.project_slot(self.head)  # new weights: the pending observation's projection is redone
         if self.check_cap and not bool(torch.isfinite(self.last_loss)):
             raise RuntimeError('BatchedMAPPO: non-finite loss (an action outside the action range or non-finite '
                                'logits in a minibatch)')
@@ -1215,22 +1067,6 @@ class BatchedMAPPO:
             self.opt.step()
         self.last_loss.copy_(loss.detach())
         self.updates += 1
-
-    def _project_slot(self, k):
-        """Slot k's fused projection redone with the current weights (BatchedA2C._project_slot0)."""
-        pb = self.pobs
-        if not pb.idx.is_cuda:
-            pb.emb[k].copy_(_project_dense(pb.idx[k], pb.val[k], self.net.obs_proj))
-            return
-        learn_lib.call('mfg_packed_project', pb.idx[k].data_ptr(), pb.val[k].data_ptr(), self.N, pb.cap,
-                       pb.wt.data_ptr(), pb.bias.data_ptr(), pb.E, pb.kdim, pb.emb[k].data_ptr(), pb.E,
-                       learn_lib.stream(self.dev))
-
-    def train(self, n_steps):
-        """n_steps env-steps (with the learn calls that fall into them); returns the last minibatch loss."""
-        for _ in range(n_steps):
-            self.step()
-        return self.last_loss
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -12,8 +12,9 @@ Reference anchors:
 ``baddbmm`` over agents. Activations are agent-major ``[A, rows, T, ...]``: one network's rows are contiguous. The
 engine's order is ``[B][A]``; the transposition happens in ``mfg_packed_project_grouped`` (include/mfg_learn.h) and in
 one small copy of the sampled actions back to the engine's ``[B][A]`` buffer. ``BatchedIAC`` / ``BatchedSEAC`` take
-``BatchedA2C``'s loop conventions unchanged (window alignment, restarts after a done, auto-reset, deferred replay,
-``check_cap``, the ``episodes`` / ``reward_sum`` counters); the learner recomputes the window with grad.
+``BatchedA2C``'s loop unchanged, from the same core (mfg_amd/rollout.py: window alignment, restarts after a done,
+auto-reset, deferred replay, ``check_cap``, the ``episodes`` / ``reward_sum`` counters); the learner recomputes the window
+with grad.
 """
 import numpy as np
 import torch
@@ -24,6 +25,7 @@ from torch.distributions import Categorical
 from . import gru_window, learn_lib
 from .gru_window import blin as _blin  # per-agent x W^T + b, the layers' GEMM (and the grouped GRU step's)
 from .marl import RecurrentAC, compute_advantages, nonfinite_to_nan
+from .rollout import WindowRollout
 
 _seac_lib = learn_lib.lib  # the former binder's name, for callers written against it
 
@@ -408,13 +410,13 @@ class _SEACHead(torch.autograd.Function):
 # ---------------------------------------------------------------------------------------------------------------------
 # the learners
 # ---------------------------------------------------------------------------------------------------------------------
-class BatchedIAC:
+class BatchedIAC(WindowRollout):
     """Independent actor-critic (``algorithms/marl/iac.py`` ``LoopIAC``) over B envs x A agents of one engine,
     everything on the device: one network per agent (``AgentNets``), each trained on its own agent's window with the
     A2C loss, RMSprop(3e-4, eps 1e-5) on the stacked parameters (elementwise, so it equals A separate optimisers) and
     ``clip_grad_norm_(0.5)`` per agent. Agents may have different action counts (``spec.n_actions``).
 
-    The loop is ``BatchedA2C``'s: entry t of the window holds (o_t, a_{t-1}) as the network input and a_t, r_t, d_t as
+    The loop is ``rollout.WindowRollout``'s, as ``BatchedA2C``'s: entry t of the window holds (o_t, a_{t-1}) as the network input and a_t, r_t, d_t as
     targets; after a done the next entry's action input is -1 and its recurrent state zero; the engine auto-resets
     and its floor-shuffle replay is deferred to the window's last step; ``episodes`` / ``reward_sum`` fold in a window
     in ``learn``; with ``check_cap`` a learn call raises on truncated packed rows and on non-finite acting logits.
@@ -430,23 +432,14 @@ class BatchedIAC:
     def __init__(self, factory, nets=None, n_steps=5, gamma=0.99, entropy_coef=0.01, vf_coef=0.5, gae_coef=0.0,
                  lr=3e-4, cap=32, obs_emb_size=96, action_emb_size=16, hidden_size=64, use_agent_embedding=False,
                  fused_head=None, check_cap=True, generator=None):
-        from .engine import PackedObs
         if use_agent_embedding:
             raise ValueError(f'{type(self).__name__}: use_agent_embedding=True is not supported')
-        self.f = factory
-        eng = factory.engine
-        self.B, self.A = eng.B, eng.A
-        self.N = self.B * self.A
-        self.dev = eng.device
         self.n_act = [int(x) for x in factory.spec.n_actions]
         if self.cross and len(set(self.n_act)) != 1:
             raise ValueError('BatchedSEAC evaluates every network on every agent\'s actions: all agents need the same '
                              'number of actions')
-        kdim = eng.lmax * eng.obs_hw[0] * eng.obs_hw[1]
-        if not check_cap and cap < kdim:
-            raise ValueError(f'check_cap=False needs cap >= lmax*h*w = {kdim} (rows can hold up to that many '
-                             f'nonzero entries); got cap {cap}')
-        self.nets = nets if nets is not None else AgentNets(kdim, self.n_act, obs_emb_size, action_emb_size,
+        super().__init__(factory, cap, check_cap, generator)
+        self.nets = nets if nets is not None else AgentNets(self.kdim, self.n_act, obs_emb_size, action_emb_size,
                                                             hidden_size, hidden_size, self.A)
         if list(self.nets.n_act) != self.n_act:
             raise ValueError(f'the networks\' action counts {self.nets.n_act} differ from the spec\'s {self.n_act}')
@@ -456,28 +449,14 @@ class BatchedIAC:
         self.opt = torch.optim.RMSprop(self.nets.agent_params(), lr=lr, eps=1e-5)
         self.T, self.gamma, self.entropy_coef, self.vf_coef, self.gae_coef = n_steps, gamma, entropy_coef, vf_coef, \
             gae_coef
-        self.check_cap, self.gen = check_cap, generator
         self.fused_head = self.fused_default if fused_head is None else bool(fused_head)
-        T, B, A, dev = self.T, self.B, self.A, self.dev
-        self.pobs = PackedObs(eng, K=T + 1, cap=cap)  # entries only: obs_proj is per agent
-        self.slot = [self.pobs.view(k) for k in range(T + 1)]
-        self.act_in = torch.full((T + 1, B, A), -1, dtype=torch.int64, device=dev)  # a_{t-1}, -1 = none
-        self.act = torch.zeros((T, B, A), dtype=torch.int32, device=dev)
-        self.rew = torch.zeros((T, B, A), dtype=torch.float64, device=dev)
-        self.done = torch.zeros((T, B), dtype=torch.uint8, device=dev)
-        Ha, Hc = self.nets.hidden_size_actor, self.nets.hidden_size_critic
-        self.h0a = torch.zeros((A, B, Ha), device=dev)  # the recurrent states fed at entry 0 of the window
-        self.h0c = torch.zeros((A, B, Hc), device=dev)
-        self.ha, self.hc = self.h0a.clone(), self.h0c.clone()
+        A, B, dev = self.A, self.B, self.dev
+        # entries only (obs_proj is per agent: no fused projection); h0a / h0c: the states fed at entry 0 of the window
+        self._alloc((self.nets.hidden_size_actor, self.nets.hidden_size_critic), agent_major=True)
         self._u = torch.empty((A, B), device=dev)
         self._act_am = torch.zeros((A, B), dtype=torch.int32, device=dev)  # the sampled actions, agent-major
         self.n_act_dev = torch.tensor(self.n_act, dtype=torch.int32, device=dev)
         self.last_loss = torch.zeros(A, device=dev)  # per network
-        self.t = 0
-        self.updates = 0
-        self.episodes = torch.zeros((), dtype=torch.float64, device=dev)
-        self.reward_sum = torch.zeros((), dtype=torch.float64, device=dev)
-        self._started = False
 
     def activation_bytes(self):
         """The learner's window memory: f32 activations kept for the backward pass, per (network, row, entry) the
@@ -485,12 +464,6 @@ class BatchedIAC:
         n_steps + 1 entries."""
         rows = self.A * self.N if self.cross else self.N
         return 4 * rows * (self.T + 1) * self.nets.entry_floats()
-
-    def reset(self):
-        self.f.engine.reset(obs=self.slot[0], init=0 if self.f._created else 1, seed_base=self.f.seed_base)
-        self.f._created = True
-        self._started = True
-        self.t = 0
 
     @torch.no_grad()
     def step(self):
@@ -501,18 +474,7 @@ class BatchedIAC:
         emb = self.nets.project(self.pobs.idx[t:t + 1], self.pobs.val[t:t + 1])  # [A, B, 1, E]
         out = self.nets.forward_emb(emb, self.act_in[t].t()[:, :, None], self.ha, self.hc)
         self._sample(out['logits'][:, :, 0], t)
-        self.f.engine.step(1, actions=self.act[t], reward=self.rew[t], done=self.done[t], obs=self.slot[t + 1],
-                           auto_reset=True, step_base=self.f.t, defer_replay=t + 1 < self.T)
-        self.f.t += 1
-        d = self.done[t].bool()
-        a = self.act[t].long()
-        self.act_in[t + 1].copy_(torch.where(d.view(-1, 1), torch.full_like(a, -1), a))
-        keep = (~d).to(self.ha.dtype).view(1, self.B, 1)  # broadcast over the agents
-        torch.mul(out['hidden_actor'][:, :, 0], keep, out=self.ha)
-        torch.mul(out['hidden_critic'][:, :, 0], keep, out=self.hc)
-        self.t += 1
-        if self.t == self.T:
-            self.learn()
+        self._window_step(out['hidden_actor'][:, :, 0], out['hidden_critic'][:, :, 0])
 
     def _sample(self, logits, t):
         """a_t ~ Categorical(logits[g, b, :n_act[g]]) into act[t] [B, A] (base_ac.py:74-76): mfg_sample_categorical on
@@ -580,13 +542,8 @@ class BatchedIAC:
 
     def learn(self):
         """One update of every network on the window (iac.py:50-57 / seac.py:49-54), then slide: o_T becomes o_0."""
-        if self.check_cap:
-            self.pobs.check()
-            if self.gen is None and self.dev.type == 'cuda' and bool((self.act < 0).any()):
-                raise RuntimeError(f'{type(self).__name__}: non-finite policy logits in this window (training '
-                                   f'diverged)')
-        self.episodes += self.done.sum()
-        self.reward_sum += self.rew.sum()
+        self._check(type(self).__name__, 'in this window')
+        self._fold()
         with torch.enable_grad():
             loss = self.loss()
             self.opt.zero_grad(set_to_none=True)
@@ -595,20 +552,9 @@ class BatchedIAC:
             self.opt.step()
         with torch.no_grad():
             self.last_loss.copy_(loss.detach())
-            T = self.T
-            self.pobs.idx[0].copy_(self.pobs.idx[T])
-            self.pobs.val[0].copy_(self.pobs.val[T])
-            self.pobs.count[0].copy_(self.pobs.count[T])
-            self.act_in[0].copy_(self.act_in[T])
-            self.h0a.copy_(self.ha)
-            self.h0c.copy_(self.hc)
+            self._slide()
         self.updates += 1
         self.t = 0
-
-    def train(self, n_updates):
-        for _ in range(n_updates * self.T):
-            self.step()
-        return self.last_loss
 
 
 class BatchedSEAC(BatchedIAC):

@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import eval_ref as R
-from test_mappo import _ScriptedEngine, pack
+from scripted import ScriptedEngine, pack
 from mfg_amd.evaluate import (BatchedEvaluator, actor_step, eval_fold, load_reference_checkpoint, natural_key,
                               sample_inversion)
 from mfg_amd.marl import AgentNets, RecurrentAC
@@ -67,7 +67,7 @@ def test_frame_is_the_reference_frame(tag):
 # the loop on a scripted engine
 # ---------------------------------------------------------------------------------------------------------------------
 def _scripted(A=2, B=3, n_episodes=3, **kw):
-    eng = _ScriptedEngine(B=B, A=A)
+    eng = ScriptedEngine(B=B, A=A)
     f = SimpleNamespace(engine=eng, spec=SimpleNamespace(n_actions=[4] * A), _created=False, seed_base=0, t=0)
     torch.manual_seed(0)
     net = RecurrentAC(4, 4, 6, 4, 5, 5, A, use_agent_embedding=False)

@@ -8,30 +8,15 @@ gradients (Adam's first step divides by |g| + eps, which amplifies gradient roun
 1e-6 absolute.
 """
 from pathlib import Path
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
 from mfg_amd.marl import (BatchedMAPPO, RecurrentAC, chunk_starts, mappo_loss, monte_carlo_returns)
+from scripted import ScriptedEngine, factory, pack  # noqa: F401 (pack: tests/test_gpu_mappo.py takes it from here)
 
 GOLD = Path(__file__).resolve().parent / 'golden' / 'marl_mappo.npz'
-
-
-def pack(obs, cap):
-    """Dense [N, T, ...] -> (idx u16, val f32) [N, T, cap] of the nonzero entries of obs.float()."""
-    flat = torch.as_tensor(obs).reshape(obs.shape[0], obs.shape[1], -1).float()
-    N, T, K = flat.shape
-    idx = torch.zeros((N, T, cap), dtype=torch.uint16)
-    val = torch.zeros((N, T, cap), dtype=torch.float32)
-    for n in range(N):
-        for t in range(T):
-            nz = torch.nonzero(flat[n, t]).flatten()
-            assert len(nz) <= cap
-            idx[n, t, :len(nz)] = nz.to(torch.uint16)
-            val[n, t, :len(nz)] = flat[n, t, nz]
-    return idx, val
 
 
 def load_case(z, i, device='cpu'):
@@ -132,49 +117,11 @@ def test_chunk_starts_episode_rule_by_brute_force():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the ring, on a scripted engine
+# the ring, on the scripted engine (tests/scripted.py)
 # ---------------------------------------------------------------------------------------------------------------------
-class _ScriptedEngine:
-    """Stands in for mfg_amd.engine.Engine on the CPU: step k (0 = the reset) renders for env b, agent a the one
-    packed entry (index a, value code(k, b, a)), rewards code + 0.5 and ends env b's episode when
-    (k + 3 b) % period == 0."""
-
-    def __init__(self, B=3, A=2, period=7):
-        self.torch = torch
-        self.B, self.A, self.period = B, A, period
-        self.device = torch.device('cpu')
-        self.lmax, self.obs_hw = 1, (2, 2)
-        self.k = 0
-
-    def code(self, k):
-        b = torch.arange(self.B).view(-1, 1)
-        a = torch.arange(self.A).view(1, -1)
-        return (1000 * k + 10 * b + a + 1).float()
-
-    def _render(self, obs):
-        v = self.code(self.k)
-        obs.idx[0].zero_()
-        obs.val[0].zero_()
-        obs.idx[0, :, :, 0] = torch.arange(self.A).to(torch.uint16)
-        obs.val[0, :, :, 0] = v
-        obs.count[0].fill_(1)
-        obs.emb[0].copy_(obs.bias + v[..., None] * obs.wt[torch.arange(self.A)][None])
-
-    def reset(self, obs=None, init=False, seed_base=0):
-        self.k = 0
-        self._render(obs)
-
-    def step(self, K, actions=None, reward=None, done=None, obs=None, auto_reset=True, step_base=0):
-        assert K == 1 and auto_reset
-        self.k += 1
-        reward.copy_(self.code(self.k).double() + 0.5)
-        done.copy_(((self.k + 3 * torch.arange(self.B)) % self.period == 0).to(torch.uint8))
-        self._render(obs)
-
-
 def _scripted(**kw):
-    eng = _ScriptedEngine()
-    f = SimpleNamespace(engine=eng, spec=SimpleNamespace(n_actions=[4] * eng.A), _created=False, seed_base=0, t=0)
+    eng = ScriptedEngine()
+    f = factory(eng, [4] * eng.A)
     args = dict(n_steps=3, buffer_size=8, batch_size=64, n_updates=1, cap=2, obs_emb_size=6, action_emb_size=4,
                 hidden_size=5, generator=torch.Generator().manual_seed(0))
     args.update(kw)
@@ -241,6 +188,7 @@ def test_batched_mappo_learns_on_the_scripted_engine():
     e = tr.net.project_packed(tr.pobs.idx[tr.head], tr.pobs.val[tr.head])
     assert torch.allclose(e, tr.pobs.emb[tr.head], rtol=1e-5, atol=1e-5)
     assert float(tr.episodes) == float(sum(((k + 3 * b) % eng.period == 0) for k in range(1, 13) for b in range(eng.B)))
+    assert eng.defer == [False] * 12  # the ring never defers the engine's floor-shuffle replay
 
 
 def test_no_valid_start_skips_the_update():
@@ -253,7 +201,6 @@ def test_no_valid_start_skips_the_update():
 def test_constructor_errors():
     with pytest.raises(ValueError, match='buffer_size'):
         _scripted(buffer_size=3, n_steps=3)
-    eng = _ScriptedEngine()
-    f = SimpleNamespace(engine=eng, spec=SimpleNamespace(n_actions=[4, 5]), _created=False, seed_base=0, t=0)
+    f = factory(ScriptedEngine(), [4, 5])
     with pytest.raises(ValueError, match='same number of actions'):
         BatchedMAPPO(f)

@@ -189,6 +189,71 @@ def test_packed_cap_truncation_is_reported():
         po.check()
 
 
+def test_a2c_window_alignment_on_the_scripted_engine():
+    """BatchedA2C's loop on the CPU (the recompute path) over the scripted engine (tests/scripted.py), period 6: env
+    0's episodes end at steps 6 and 12, each a window's last step (a restart across the slide), the other envs' inside
+    windows. Every window holds the steps it should, the learner's forward of it reproduces the acting logits (rtol
+    1e-4, atol 1e-5: tests/test_seac.py's bound for the same comparison), and the slide, the counters and the deferred
+    replay are what mfg_amd/rollout.py says."""
+    from mfg_amd.marl import BatchedA2C
+    from scripted import ScriptedEngine, factory
+    eng = ScriptedEngine(period=6)
+    torch.manual_seed(0)
+    tr = BatchedA2C(factory(eng, [4] * eng.A), n_steps=3, cap=2, obs_emb_size=6, action_emb_size=4, hidden_size=5,
+                    generator=torch.Generator().manual_seed(0))
+    assert not tr.reuse
+    A, B, T, N = tr.A, tr.B, tr.T, tr.N
+    acting, windows = [], []
+    sample, learn = tr._sample, tr.learn
+
+    def spy_sample(logits, t):
+        acting.append(logits.clone())
+        sample(logits, t)
+
+    def spy_learn():
+        k0 = eng.k - T  # the step that rendered entry 0 of this window
+        for s in range(T + 1):
+            assert torch.equal(tr.pobs.val[s, :, :, 0], eng.code(k0 + s))
+        for s in range(T):
+            assert torch.equal(tr.rew[s], eng.code(k0 + s + 1).double() + 0.5)
+            d = (k0 + s + 1 + 3 * torch.arange(B)) % eng.period == 0
+            assert torch.equal(tr.done[s].bool(), d)
+            assert torch.equal(tr.act_in[s + 1], torch.where(d.view(-1, 1), torch.full((B, A), -1), tr.act[s].long()))
+            assert bool(((tr.act[s] >= 0) & (tr.act[s] < 4)).all())
+        for h in (tr.ha, tr.hc):  # d: the window's last step
+            live = h.view(B, A, -1).ne(0).any(-1)
+            assert torch.equal(live, (~d).view(-1, 1).expand(B, A))
+        # no weight has changed since the window's first step: the learner's forward reproduces the acting logits
+        idx, val, a_in, _, starts, _, _ = tr.window()
+        with torch.no_grad():
+            out = tr.net.forward_emb(tr.net.project_packed(idx, val), a_in, tr.h0a, tr.h0c, agent_ids=tr.agent_ids,
+                                     starts=starts)
+        assert torch.allclose(out['logits'][:, :T], torch.stack(acting[-T:], 1), rtol=1e-4, atol=1e-5)
+        w0 = [p.detach().clone() for p in tr.net.parameters()]
+        ha, hc = tr.ha.clone(), tr.hc.clone()
+        learn()
+        windows.append(1)
+        assert any(not torch.equal(p0, p.detach()) for p0, p in zip(w0, tr.net.parameters()))
+        assert bool(torch.isfinite(tr.last_loss))
+        pb = tr.pobs
+        assert torch.equal(pb.idx[0].long(), pb.idx[T].long()) and torch.equal(pb.val[0], pb.val[T])
+        assert torch.equal(pb.count[0], pb.count[T]) and torch.equal(tr.act_in[0], tr.act_in[T])
+        assert torch.equal(tr.h0a, ha) and torch.equal(tr.h0c, hc) and tr.t == 0
+        # the engine projects with the new weights, and o_0 was re-projected with them
+        assert torch.equal(pb.wt, tr.net.obs_proj.weight.detach().t())
+        with torch.no_grad():
+            e = tr.net.project_packed(pb.idx[0], pb.val[0])
+        assert torch.allclose(e, pb.emb[0], rtol=1e-5, atol=1e-5)
+
+    tr._sample, tr.learn = spy_sample, spy_learn
+    tr.train(4)
+    assert len(windows) == 4 and tr.updates == 4
+    assert eng.defer == [True, True, False] * 4  # the replay is deferred to the window's last step
+    ks = range(1, 4 * T + 1)
+    assert float(tr.episodes) == float(sum((k + 3 * b) % eng.period == 0 for k in ks for b in range(B)))
+    assert float(tr.reward_sum) == float(sum((eng.code(k).double() + 0.5).sum() for k in ks))
+
+
 @pytest.mark.gpu
 def test_batched_a2c_trains_on_device():
     from mfg_amd.factory import BatchedFactory

@@ -8,7 +8,6 @@ gradients rtol 1e-4 / atol 1e-6; the optimiser step (per-agent clip_grad_norm_(0
 stacked parameters) is pinned on the fixture's own gradients, weights within 1e-6 absolute.
 """
 from pathlib import Path
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -16,7 +15,7 @@ import torch
 
 from mfg_amd.marl import (AgentNets, BatchedA2C, BatchedIAC, BatchedSEAC, RecurrentAC, a2c_loss_terms, iac_loss_terms,
                           seac_loss_terms)
-from test_mappo import _ScriptedEngine, pack
+from scripted import ScriptedEngine, factory, pack
 
 GOLD = Path(__file__).resolve().parent / 'golden' / 'marl_seac.npz'
 CASES = [0, 1, 2]
@@ -202,29 +201,20 @@ def test_padded_action_heads_get_no_gradient():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the loop, on the scripted engine of tests/test_mappo.py
+# the loop, on the scripted engine (tests/scripted.py)
 # ---------------------------------------------------------------------------------------------------------------------
-class _ScriptedPacked(_ScriptedEngine):
-    """The scripted engine rendering packed entries only (the per-agent learners build PackedObs without the fused
-    projection) and taking the deferred-replay flag."""
+class _ScriptedPacked(ScriptedEngine):
+    """The scripted engine rendering packed entries only: the per-agent learners build PackedObs without the fused
+    projection."""
 
     def _render(self, obs):
         assert obs.emb is None and obs.wt is None
-        v = self.code(self.k)
-        obs.idx[0].zero_()
-        obs.val[0].zero_()
-        obs.idx[0, :, :, 0] = torch.arange(self.A).to(torch.uint16)
-        obs.val[0, :, :, 0] = v
-        obs.count[0].fill_(1)
-
-    def step(self, K, defer_replay=False, **kw):
-        self.defer = getattr(self, 'defer', []) + [bool(defer_replay)]
-        super().step(K, **kw)
+        super()._render(obs)
 
 
 def _scripted(cls, n_actions=(4, 4), **kw):
     eng = _ScriptedPacked()
-    f = SimpleNamespace(engine=eng, spec=SimpleNamespace(n_actions=list(n_actions)), _created=False, seed_base=0, t=0)
+    f = factory(eng, n_actions)
     args = dict(n_steps=3, cap=2, obs_emb_size=6, action_emb_size=4, hidden_size=5,
                 generator=torch.Generator().manual_seed(0))
     args.update(kw)
@@ -282,8 +272,7 @@ def test_constructor_errors():
     with pytest.raises(ValueError, match='same number of actions'):
         _scripted(BatchedSEAC, (4, 5))
     _scripted(BatchedIAC, (4, 5))  # independent networks take different counts
-    eng = _ScriptedPacked()
-    f = SimpleNamespace(engine=eng, spec=SimpleNamespace(n_actions=[4, 5]), _created=False, seed_base=0, t=0)
+    f = factory(_ScriptedPacked(), [4, 5])
     with pytest.raises(ValueError, match='same number of actions'):
         BatchedA2C(f)  # the shared-network learner still refuses such a team
     with pytest.raises(ValueError, match='use_agent_embedding'):
