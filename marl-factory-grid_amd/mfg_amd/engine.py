@@ -88,6 +88,18 @@ def load_lib():
     L.mfg_info_eval_host.argtypes = prog + [C.c_void_p] * 7
     for f in ('create', 'destroy', 'config', 'step', 'episodes', 'rows', 'drain', 'reset', 'eval_host'):
         getattr(L, 'mfg_info_' + f).restype = C.c_int
+    # include/mfg_record.h
+    L.mfg_record_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int,
+                                    C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.mfg_record_destroy.argtypes = [C.c_void_p]
+    L.mfg_record_config.argtypes = [C.c_void_p, C.c_void_p]
+    L.mfg_record_step.argtypes = [C.c_void_p] * 7
+    L.mfg_record_drain.argtypes = [C.c_void_p] * 4
+    L.mfg_record_occupancy.argtypes = [C.c_void_p] * 3
+    L.mfg_record_clear_occupancy.argtypes = [C.c_void_p] * 2
+    L.mfg_record_env_state.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    for f in ('create', 'destroy', 'config', 'step', 'drain', 'occupancy', 'clear_occupancy', 'env_state'):
+        getattr(L, 'mfg_record_' + f).restype = C.c_int
     L.mfg_abi_version.restype = C.c_int
     if L.mfg_abi_version() != abi.ABI_VERSION:
         raise RuntimeError('libmfg_hip.so ABI version mismatch')
@@ -297,6 +309,109 @@ class InfoMonitor:
         assert got.value == n, 'episodes finished between the count and the drain on one stream'
         order = np.lexsort((hdr[:, 1], hdr[:, 0]))
         return hdr[order], s[order], c[order], n - keep
+
+
+RECORD_CFG = ['row_words', 'n_sel', 'capacity', 'row_waves', 'row_grid', 'occ_threads', 'occ_envs', 'occ_grid',
+              'occ_path', 'occ_lds_bytes', 'o_cell', 'o_act', 'o_bat', 'o_door', 'o_items', 'item_cap']  # MFG_RECORD_CFG_*
+OCC_OFF, OCC_LDS, OCC_GLOBAL = 0, 1, 2  # MFG_RECORD_OCC_*
+RECORD_MAX_CAPACITY, RECORD_MAX_EPISODES = 1 << 20, 4096
+
+
+def check_record_args(n_envs, envs, capacity, episodes=None):
+    """The selection arguments of a state recorder as (envs int32 [n_sel], capacity, episodes int32 [n_ep] or None);
+    raises ValueError for env ids out of range or given twice, a capacity outside 1 .. 2^20 or episode numbers < 1."""
+    ids = [int(b) for b in envs]
+    for b in ids:
+        if not 0 <= b < int(n_envs):
+            raise ValueError(f'env id {b} out of range: the batch has {int(n_envs)} envs')
+    if len(set(ids)) != len(ids):
+        raise ValueError('an env id is selected twice')
+    if not 1 <= int(capacity) <= RECORD_MAX_CAPACITY:
+        raise ValueError(f'capacity must be 1 .. {RECORD_MAX_CAPACITY}')
+    eps = None
+    if episodes:
+        eps = [int(x) for x in episodes]
+        if min(eps) < 1 or len(eps) > RECORD_MAX_EPISODES:
+            raise ValueError(f'episodes are 1-based episode numbers, at most {RECORD_MAX_EPISODES} of them')
+        eps = np.asarray(eps, np.int32)
+    return np.asarray(ids, np.int32), int(capacity), eps
+
+
+class StateRecorder:
+    """The device state recorder over one `Engine` (include/mfg_record.h): fixed-width state rows of the selected
+    envs and the agents' cell-visit counts of the whole batch, one `step` call after each K = 1 `Engine.step` made
+    with auto_reset=False. No CPU fallback. occ_lds_cells: test-only bound of the LDS histogram path."""
+
+    def __init__(self, engine, envs, capacity=256, episodes=None, occupancy=True, occ_lds_cells=0):
+        self.envs, self.capacity, eps = check_record_args(engine.B, envs, capacity, episodes)
+        self.torch = engine.torch
+        self.L = engine.L
+        self.engine = engine
+        self.B, self.A = engine.B, engine.A
+        self.device = engine.device
+        self.episodes = eps
+        self.occupancy = bool(occupancy)
+        self.HW = engine.spec.H * engine.spec.W
+        h = C.c_void_p()
+        _check(self.L.mfg_record_create(engine.h, C.byref(engine.spec.c), self.envs.ctypes.data, len(self.envs),
+                                        self.capacity, None if eps is None else eps.ctypes.data,
+                                        0 if eps is None else len(eps), int(self.occupancy), int(occ_lds_cells),
+                                        C.byref(h)), 'mfg_record_create')
+        self.h = h
+        cfg = np.zeros(len(RECORD_CFG), np.int32)
+        _check(self.L.mfg_record_config(self.h, cfg.ctypes.data), 'mfg_record_config')
+        self.config = dict(zip(RECORD_CFG, (int(x) for x in cfg)))
+        self.row_words = self.config['row_words']
+
+    def close(self):
+        if getattr(self, 'h', None) is not None and self.h.value:
+            self.L.mfg_record_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def step(self, actions, ev_act, ev_watch, ev_misc, done):
+        """Record the step the engine just made (auto_reset=False) from that call's buffers. Stream-ordered, no sync."""
+        BA = self.B * self.A
+        for t, n, dt in ((actions, BA, self.torch.int32), (ev_act, BA, self.torch.uint8),
+                         (ev_watch, BA, self.torch.uint8), (ev_misc, self.B * EV_MISC, self.torch.int32),
+                         (done, self.B, self.torch.uint8)):
+            if t is None or t.numel() != n or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f'buffer must be a contiguous {dt} tensor of {n} elements on {self.device}')
+        _check(self.L.mfg_record_step(self.h, _ptr(actions), _ptr(ev_act), _ptr(ev_watch), _ptr(ev_misc), _ptr(done),
+                                      self._stream()), 'mfg_record_step')
+
+    def drain(self):
+        """(rows uint32 [n_sel, capacity, row_words], counts uint32 [n_sel]) as numpy arrays: of selected env s (the
+        order of `envs`) rows [s, :min(counts[s], capacity)] are valid, counts past the capacity were dropped. The
+        device counters restart at 0 (one sync)."""
+        rows = np.zeros((len(self.envs), self.capacity, self.row_words), np.uint32)
+        counts = np.zeros(len(self.envs), np.uint32)
+        _check(self.L.mfg_record_drain(self.h, rows.ctypes.data, counts.ctypes.data, self._stream()),
+               'mfg_record_drain')
+        return rows, counts
+
+    def occupancy_map(self):
+        """uint64 [H * W] cell-visit counts since the last clear (one sync)."""
+        out = np.zeros(self.HW, np.uint64)
+        _check(self.L.mfg_record_occupancy(self.h, out.ctypes.data, self._stream()), 'mfg_record_occupancy')
+        return out
+
+    def clear_occupancy(self):
+        _check(self.L.mfg_record_clear_occupancy(self.h, self._stream()), 'mfg_record_clear_occupancy')
+
+    def env_state(self, env):
+        """One env's state record as numpy bytes (one sync), e.g. for a `RecordView`."""
+        out = np.zeros(self.engine.layout['size'], np.uint8)
+        _check(self.L.mfg_record_env_state(self.h, int(env), out.ctypes.data, self._stream()), 'mfg_record_env_state')
+        return out
 
 
 class PackedObs:

@@ -19,6 +19,9 @@
 * `BatchedEnvMonitor` -- `EnvMonitor` for a `BatchedFactory` / `VectorFactory`: every env's info dict evaluated
   and folded per episode on the device by one kernel per step (include/mfg_info.h, engine.InfoMonitor);
   `frame()` is the reference's monitor DataFrame with one row per finished episode of any env.
+* `BatchedEnvRecorder` -- `EnvRecorder` for a `BatchedFactory`: the chosen envs' per-step states as device rows and
+  the whole batch's occupation map, folded by two kernels per step (include/mfg_record.h, engine.StateRecorder);
+  `records(env=b)` is the reference's record dict of that env, decoded from the rows (mfg_amd/record_rows.py).
 """
 import json
 import pickle
@@ -153,22 +156,30 @@ class EnvRecorder(_Wrapper):
                 for a in st.get('agents', []):
                     if 0 <= a['x'] < H and 0 <= a['y'] < W:
                         occ[a['x'], a['y']] += 1
-        if out_stem is not None:
-            out_stem = Path(out_stem)
-            np.save(out_stem.with_suffix('.npy'), occ)
-            try:
-                import matplotlib
-                matplotlib.use('Agg')
-                import matplotlib.pyplot as plt
-            except Exception:
-                return occ
-            fig, ax = plt.subplots(figsize=(6, 6 * H / max(W, 1) + 0.5))
-            im = ax.imshow(occ, cmap='viridis')
-            fig.colorbar(im, ax=ax)
-            ax.set_title('agent occupation')
-            fig.savefig(out_stem.with_suffix('.png'))
-            plt.close(fig)
-        return occ
+        return _write_occupation(occ, out_stem)
+
+
+def _write_occupation(occ, out_stem=None):
+    """With out_stem: the [H, W] map to <out_stem>.npy and, if matplotlib is importable, a heatmap to
+    <out_stem>.png. Returns the map."""
+    import numpy as np
+    H, W = occ.shape
+    if out_stem is not None:
+        out_stem = Path(out_stem)
+        np.save(out_stem.with_suffix('.npy'), occ)
+        try:
+            import matplotlib
+            matplotlib.use('Agg')
+            import matplotlib.pyplot as plt
+        except Exception:
+            return occ
+        fig, ax = plt.subplots(figsize=(6, 6 * H / max(W, 1) + 0.5))
+        im = ax.imshow(occ, cmap='viridis')
+        fig.colorbar(im, ax=ax)
+        ax.set_title('agent occupation')
+        fig.savefig(out_stem.with_suffix('.png'))
+        plt.close(fig)
+    return occ
 
 
 def _deltas(t1, t2):
@@ -318,6 +329,191 @@ class BatchedEnvMonitor(_Wrapper):
 
     def close(self):
         self.monitor.close()
+        self.env.close()
+
+
+class BatchedEnvRecorder(_Wrapper):
+    """`EnvRecorder` for a `BatchedFactory` (any obs_dtype): the state of the selected `envs` after every step, kept
+    on the device as fixed-width rows (engine.StateRecorder, include/mfg_record.h), and with `occupancy` the cell-visit
+    counts of the agents of ALL envs; no per-step host copy and no host sync.
+
+    `step` splits the factory's step so that a done step's state can still be read: the engine steps without
+    auto-reset, the recorder kernel reads the records, then the done envs are reset and the observations rendered,
+    all on the factory's stream. What it returns equals `BatchedFactory.step`, value for value.
+
+    Rows wait in a device ring of `capacity` rows per selected env. With `auto_drain` the wrapper fetches them before
+    the ring could fill (one drain, and one sync, per `capacity` steps); with `auto_drain=False` draining is the
+    caller's (`drain()`), and rows that found the ring full are counted in `dropped` (`dropped_by_env` per env).
+    `episodes`: record only these 1-based episode numbers of each env (the reference's `episodes` list).
+
+    Departure from the reference: `EnvRecorder` forgets its episode list at every `reset()` (recorder.py:35-36) and
+    numbers an unfinished tail `len(list)` (:63-66). Here every recorded episode is kept and `episode_nr` is always
+    the env's own 1-based episode number, for an unfinished tail too. A crashed step (a reference crash path) has no
+    state in the reference: it closes the episode without a step dict and counts in `crashed_steps`."""
+
+    def __init__(self, env, envs, filepath=None, episodes=None, capacity=256, occupancy=True, auto_drain=True,
+                 occ_lds_cells=0):
+        from .engine import check_record_args
+        ids, capacity, _ = check_record_args(env.B, envs, capacity, episodes)  # before any device work
+        super().__init__(env)
+        from .engine import StateRecorder
+        self.filepath = filepath
+        self.envs = [int(b) for b in ids]
+        self.episodes = list(episodes) if episodes else None
+        self.capacity = capacity
+        self.auto_drain = bool(auto_drain)
+        self.recorder = StateRecorder(env.engine, ids, capacity=capacity, episodes=episodes, occupancy=occupancy,
+                                      occ_lds_cells=occ_lds_cells)
+        self._rows = {b: [] for b in self.envs}  # per env: drained row blocks, in step order
+        self._since_drain = 0
+        self.dropped = 0
+        self.dropped_by_env = {b: 0 for b in self.envs}
+
+    def reset(self, mask=None):
+        return self.env.reset(mask=mask)
+
+    def step(self, actions):
+        bf = self.env
+        if not bf._created:
+            raise RuntimeError('call reset() first')
+        a = actions.to(device=bf.device, dtype=bf.torch.int32).contiguous()
+        if a.shape != (bf.B, bf.spec.n_agents):
+            raise ValueError(f'actions must be [{bf.B}, {bf.spec.n_agents}]')
+        if self.auto_drain and self._since_drain >= self.capacity:
+            self.drain()
+        bf.engine.step(1, actions=a, reward=bf.reward, done=bf.done, obs=None, ev_act=bf.ev_act, ev_watch=bf.ev_watch,
+                       ev_misc=bf.ev_misc, auto_reset=False, step_base=bf.t)
+        self.recorder.step(a, bf.ev_act, bf.ev_watch, bf.ev_misc, bf.done)
+        # a masked reset renders the observations of every env (include/mfg.h, mfg_reset)
+        bf.engine.reset(obs=bf.obs, mask=bf.done, init=0)
+        bf.t += 1
+        self._since_drain += 1
+        return bf.obs, bf.reward, bf.done, (bf.ev_act, bf.ev_watch, bf.ev_misc)
+
+    def drain(self):
+        """Fetch the rows recorded since the last drain (one sync); returns the number of rows dropped since then."""
+        rows, counts = self.recorder.drain()
+        lost = 0
+        for s, b in enumerate(self.envs):
+            n = min(int(counts[s]), self.capacity)
+            if n:
+                self._rows[b].append(rows[s, :n].copy())
+            self.dropped_by_env[b] += int(counts[s]) - n
+            lost += int(counts[s]) - n
+        self.dropped += lost
+        self._since_drain = 0
+        return lost
+
+    def rows(self, env):
+        """uint32 [n, row_words]: every row of env `env` recorded so far, in step order (drains first)."""
+        import numpy as np
+        if env not in self._rows:
+            raise KeyError(f'env {env} is not recorded (recorded: {self.envs})')
+        self.drain()
+        blocks = self._rows[env]
+        if len(blocks) > 1:
+            self._rows[env] = blocks = [np.concatenate(blocks)]
+        return blocks[0] if blocks else np.zeros((0, self.recorder.row_words), np.uint32)
+
+    def _episodes(self, env):
+        """([{'steps': [...], 'episode_nr': n}], crashed steps) of env's rows: every step dict is
+        `views.summarize_state` of the row's `Snapshot`."""
+        from . import views
+        from .record_rows import row_fields, row_snapshot
+        spec, layout = self.env.spec, self.env.engine.layout
+        out, cur, cur_nr, crashed_steps = [], [], None, 0
+
+        def close():
+            nonlocal cur
+            if cur:
+                out.append({'steps': cur, 'episode_nr': cur_nr})
+            cur = []
+
+        for row in self.rows(env):
+            _, ep, _, done, crashed = row_fields(row)
+            if cur_nr is not None and ep != cur_nr:  # (an episode the filter cut short, or a caller's reset)
+                close()
+            cur_nr = ep
+            if crashed:
+                crashed_steps += 1
+                close()
+                continue
+            cur.append(views.summarize_state(spec, row_snapshot(spec, layout, row)))
+            if done:
+                close()
+        close()
+        return out, crashed_steps
+
+    def _record_view(self, env):
+        from .engine import RecordView
+        return RecordView(self.recorder.env_state(env), self.env.engine.layout, self.env.spec)
+
+    def records(self, env):
+        """`EnvRecorder.records()`'s dict for one recorded env: {'episodes', 'n_episodes', 'metadata', 'header'}, plus
+        'crashed_steps'. The header is `views.summarize_header` of the env's current record (one host copy)."""
+        from . import views
+        import yaml
+        episodes, crashed_steps = self._episodes(env)
+        view = self._record_view(env)
+        with open(self.env.spec.config_path) as f:
+            params = yaml.safe_load(f)
+        return {'episodes': episodes, 'n_episodes': view.hdr('episode') + 1,
+                'metadata': dict(level_name=params['General']['level_name'], n_agents=len(params['Agents']),
+                                 env_seed=params['General'].get('env_seed', 69),
+                                 pomdp_r=params['General']['pomdp_r'], individual_rewards=True),
+                'header': views.summarize_header(self.env.spec, views.snapshot_from_record(view, None)),
+                'crashed_steps': crashed_steps}
+
+    @property
+    def crashed_steps(self):
+        return sum(self._episodes(b)[1] for b in self.envs)
+
+    def save_records(self, filepath=None, env=None, only_deltas=False, save_occupation_map=False,
+                     save_trajectory_map=False):
+        """JSON like `EnvRecorder.save_records`; env=None writes one file per recorded env, '_env{b}' in the stem.
+        Returns the path (or the list of paths)."""
+        filepath = Path(filepath or self.filepath)
+        filepath.parent.mkdir(exist_ok=True, parents=True)
+        paths = []
+        for b in (self.envs if env is None else [env]):
+            rec = self.records(b)
+            if only_deltas:
+                eps = rec['episodes']
+                rec['episodes'] = [_deltas(x, y) for x, y in zip(eps, eps[1:])]
+            path = filepath if env is not None else filepath.with_name(f'{filepath.stem}_env{b}{filepath.suffix}')
+            with path.open('w') as f:
+                json.dump(rec, f, default=str)
+            paths.append(path)
+        if save_occupation_map:
+            self.occupation_map(filepath.with_name(filepath.stem + '_occupation'))
+        if save_trajectory_map:
+            raise NotImplementedError('This has not yet been implemented.')  # as the reference (recorder.py:189-190)
+        return paths[0] if env is not None else paths
+
+    def occupation_map(self, out_stem=None):
+        """[H, W] int64 counts of the agents' positions over every env of the batch and every step since the last
+        `clear_occupation()`; written like `EnvRecorder.occupation_map` with out_stem."""
+        import numpy as np
+        spec = self.env.spec
+        occ = self.recorder.occupancy_map().astype(np.int64).reshape(spec.H, spec.W)
+        return _write_occupation(occ, out_stem)
+
+    def clear_occupation(self):
+        self.recorder.clear_occupancy()
+
+    def trajectory(self, env, episode):
+        """int array [T, A, 2]: the agents' (x, y) over the recorded steps of env's episode `episode` (1-based)."""
+        import numpy as np
+        from .record_rows import row_cells, row_fields
+        spec, layout = self.env.spec, self.env.engine.layout
+        cells = [row_cells(spec, layout, r) for r in self.rows(env) if row_fields(r)[1] == episode]
+        if not cells:
+            return np.zeros((0, spec.n_agents, 2), np.int64)
+        c = np.stack(cells).astype(np.int64)
+        return np.stack([c // spec.W, c % spec.W], axis=-1)
+
+    def close(self):
+        self.recorder.close()
         self.env.close()
 
 
