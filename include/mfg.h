@@ -340,6 +340,24 @@ int mfg_step(mfg_engine* e, int K, const int32_t* actions, uint32_t philox_seed,
 /* Replay pending membership-only floor shuffles (check_pos_validity, states.py:259-270, Q3). */
 int mfg_replay(mfg_engine* e, void* stream);
 
+/* The action mask of every env: out u32 [n_envs][n_agents] (device). Bit s of out[b][a] is set exactly when
+ * s < n_actions[a] and an mfg_step of env b from its record as it stands, with agent a executing slot s before any
+ * other agent has acted, would report the action valid (ev_act 0x80 | 1): a pure function of the record and the spec
+ * (no built-in rule acts before the agents), one read-only kernel (MFG_K_ACTION_MASK), nothing written but out.
+ *   Noop            1
+ *   Move            the target is not the agent's cell, holds no wall, no closed door and no blocking agent; for an
+ *                   agent with agent_blocking, also no collider (agent, maintainer) at all
+ *   DoorUse         a present door on a non-wall cell of the 3x3 around the agent
+ *   ItemAction      no live drop-off on the agent's cell and a live item on it (on a drop-off it fails: Q8)
+ *   Charge          a live pod on the cell, the agent's battery below 1.0, and no other agent on the cell
+ *   Clean           a present dirt pile on the cell
+ *   DestAction      0 (it fails off a destination and crashes the env on one, Q17)
+ *   MachineAction   0 (the step reports it invalid, Q18)
+ * A paralysed agent (its action is skipped) and every agent of a crashed env have no bit set. Within one step an
+ * earlier agent can still invalidate a later agent's action (a door it toggles, a blocking agent that moves in): the
+ * mask is exact for the first agent to act and a sound filter for the others. */
+int mfg_action_mask(mfg_engine* e, uint32_t* out, void* stream);
+
 /* Per-env state record layout (offsets) for host-side decoding, then the engine's launch facts (LDS slices,
  * o_logic, reset_overlap: 1 when a step's resets and their render run on the engine's second stream beside the
  * render of the other envs, obs_geo_r, obs_narrow, and last the render's shape: obs_maxpts, the ray length (MAXPTS)
@@ -351,11 +369,11 @@ int64_t mfg_state_bytes(const mfg_engine* e);
 /* Per-kernel timing (HIP events recorded around every launch on the launch stream while enabled).
  * Kernel ids: MFG_K_LOGIC, MFG_K_RESETDONE, MFG_K_OBS, MFG_K_REPLAY, MFG_K_RESET, MFG_K_OBS_DONE (the render of
  * the envs reset in a step, on the engine's second stream; mfg_step with auto_reset and obs), MFG_K_REPLAY_SEL (the
- * debt of envs whose RespawnDirt fires in the coming step, paid before k_logic).
+ * debt of envs whose RespawnDirt fires in the coming step, paid before k_logic), MFG_K_ACTION_MASK (mfg_action_mask).
  * mfg_profile_read synchronises on the last event, writes total milliseconds and launch counts per
  * kernel id (n entries, up to MFG_K_COUNT) and clears the accumulators. */
 enum { MFG_K_LOGIC = 0, MFG_K_RESETDONE = 1, MFG_K_OBS = 2, MFG_K_REPLAY = 3, MFG_K_RESET = 4, MFG_K_OBS_DONE = 5,
-       MFG_K_REPLAY_SEL = 6, MFG_K_COUNT = 7 };
+       MFG_K_REPLAY_SEL = 6, MFG_K_ACTION_MASK = 7, MFG_K_COUNT = 8 };
 int mfg_profile(mfg_engine* e, int enable);
 int mfg_profile_read(mfg_engine* e, double* total_ms, int64_t* launches, int n);
 /* Snapshots (checkpoint / resume, parity fixtures): whole state buffer device <-> device. */

@@ -1,5 +1,6 @@
-// Evaluation-side kernels (mfg_amd/evaluate.py BatchedEvaluator; include/mfg_learn.h):
+// Evaluation-side kernels (mfg_amd/evaluate.py BatchedEvaluator; include/mfg_learn.h, include/mfg_act.h):
 //   mfg_policy_act: one acting step of RecurrentAC's actor (networks.py:50-69 without the critic) as ONE kernel,
+//                   and with an action mask mfg_policy_act_masked (mfg_policy_act is its NULL-mask case),
 //   mfg_eval_fold:  the per-step episode bookkeeping of eval_loop (base_ac.py:152-183) as ONE kernel.
 //
 // mfg_policy_act. A block of 256 threads owns a tile of 32 rows (env, agent) of one network; wave w owns rows
@@ -14,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/mfg_learn.h"
+#include "../../include/mfg_act.h"
 #include "mfg_learn_device.h"
 
 namespace {
@@ -94,7 +96,7 @@ struct ActArgs {
   mfg_actor_weights w;
   const int32_t* n_act; const int32_t* prev_action; const uint8_t* prev_done;
   float* h; int64_t h_env, h_agent;
-  const float* u; int greedy; int32_t* act_out; float* logits_out;
+  const float* u; int greedy; const uint32_t* mask; int32_t* act_out; float* logits_out;
   int64_t rows_per_group;
 };
 
@@ -215,17 +217,25 @@ __global__ void __launch_bounds__(256) k_policy_act(const ActArgs p) {
       int64_t b; int i;
       row_env_agent(p.g, A, q, b, i);
       const int64_t row = b * A + i;
-      const float* l = bufB + tid * lsB;
+      float* l = bufB + tid * lsB;
       const int n_act = p.n_act[net];
+      if (p.logits_out)  // the raw logits, before the mask touches the row
+        for (int a = 0; a < NM; a++) p.logits_out[row * NM + a] = l[a];
       int pick = -1;
       if (n_act >= 1 && n_act <= NM) {
+        // masked acting: the cleared bits' logits become -inf in this row's LDS copy (only this thread reads it from
+        // here on), unless the word has no bit set among the row's n_act
+        if (p.mask) {
+          const uint32_t m = p.mask[row] & (n_act >= 32 ? 0xFFFFFFFFu : (1u << n_act) - 1u);
+          if (m)
+            for (int a = 0; a < n_act; a++)
+              if (!((m >> a) & 1)) l[a] = -INFINITY;
+        }
         float mx, s;
         row_max_expsum(l, n_act, mx, s);
         if (s > 0.0f && !isinf(s)) pick = row_pick(l, n_act, mx, s, p.greedy != 0, p.greedy ? 0.0f : p.u[row]);
       }
       p.act_out[row] = pick;
-      if (p.logits_out)
-        for (int a = 0; a < NM; a++) p.logits_out[row * NM + a] = l[a];
     }
   }
 }
@@ -263,11 +273,11 @@ __global__ void __launch_bounds__(256) k_eval_fold(const double* __restrict__ re
 
 }  // namespace
 
-extern "C" int mfg_policy_act(const float* emb, int64_t emb_env, int64_t emb_agent, int64_t n_envs, int n_agents, int g,
-                              int e_dim, int ae_dim, int hd, int n_max, const mfg_actor_weights* w,
-                              const int32_t* n_act, const int32_t* prev_action, const uint8_t* prev_done, float* h,
-                              int64_t h_env, int64_t h_agent, const float* u, int greedy, int32_t* act_out,
-                              float* logits_out, void* stream) {
+extern "C" int mfg_policy_act_masked(const float* emb, int64_t emb_env, int64_t emb_agent, int64_t n_envs, int n_agents,
+                                     int g, int e_dim, int ae_dim, int hd, int n_max, const mfg_actor_weights* w,
+                                     const int32_t* n_act, const int32_t* prev_action, const uint8_t* prev_done,
+                                     float* h, int64_t h_env, int64_t h_agent, const float* u, int greedy,
+                                     const uint32_t* mask, int32_t* act_out, float* logits_out, void* stream) {
   if (!emb || !w || !n_act || !h || !act_out || (!greedy && !u)) return -1;
   if (n_envs <= 0 || n_agents <= 0 || (g != 1 && g != n_agents)) return -1;
   if (e_dim < 1 || e_dim > MAX_E || ae_dim < 1 || ae_dim > MAX_AE || hd < 1 || hd > MAX_H || n_max < 1 ||
@@ -280,7 +290,7 @@ extern "C" int mfg_policy_act(const float* emb, int64_t emb_env, int64_t emb_age
   a.w = *w;
   a.n_act = n_act; a.prev_action = prev_action; a.prev_done = prev_done;
   a.h = h; a.h_env = h_env; a.h_agent = h_agent;
-  a.u = u; a.greedy = greedy; a.act_out = act_out; a.logits_out = logits_out;
+  a.u = u; a.greedy = greedy; a.mask = mask; a.act_out = act_out; a.logits_out = logits_out;
   a.rows_per_group = g > 1 ? n_envs : n_envs * n_agents;
   const int64_t nbx = (a.rows_per_group + TILE - 1) / TILE;
   const int nby = g > 1 ? n_agents : 1;
@@ -290,6 +300,17 @@ extern "C" int mfg_policy_act(const float* emb, int64_t emb_env, int64_t emb_age
   const size_t lds = (size_t)TILE * (pad4(first) + pad4(wide) + pad4(hd)) * sizeof(float);
   hipLaunchKernelGGL(k_policy_act, dim3((unsigned)nbx, (unsigned)nby), dim3(256), lds, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// the NULL-mask case of the same kernel
+extern "C" int mfg_policy_act(const float* emb, int64_t emb_env, int64_t emb_agent, int64_t n_envs, int n_agents, int g,
+                              int e_dim, int ae_dim, int hd, int n_max, const mfg_actor_weights* w,
+                              const int32_t* n_act, const int32_t* prev_action, const uint8_t* prev_done, float* h,
+                              int64_t h_env, int64_t h_agent, const float* u, int greedy, int32_t* act_out,
+                              float* logits_out, void* stream) {
+  return mfg_policy_act_masked(emb, emb_env, emb_agent, n_envs, n_agents, g, e_dim, ae_dim, hd, n_max, w, n_act,
+                               prev_action, prev_done, h, h_env, h_agent, u, greedy, nullptr, act_out, logits_out,
+                               stream);
 }
 
 extern "C" int mfg_eval_fold(const double* reward, const uint8_t* done, int64_t n_envs, int n_agents, int n_episodes,

@@ -1168,6 +1168,26 @@ static int step_impl(mfg_engine* e, int K, const int32_t* actions, uint32_t phil
   return defer ? 0 : replay_impl(e, stream);
 }
 
+// The action mask of every env from its record as it stands (k_action_mask): one launch, the step prefix of each env as
+// the wave's LDS slice, nothing written but out.
+static int action_mask_impl(mfg_engine* e, uint32_t* out, void* stream) {
+  if (!out) return fail("mfg_action_mask: out is NULL");
+  hipStream_t st = (hipStream_t)stream;
+  PROF_BEGIN(e, st);
+  const int lds = e->h.L.o_logic;
+  if (e->h.lane_passes == 2)
+    hipLaunchKernelGGL(k_action_mask<2>, GEOM(lds), st, e->d_spec, (const uint8_t*)e->d_state, (long long)e->B, out);
+  else
+    hipLaunchKernelGGL(k_action_mask<1>, GEOM(lds), st, e->d_spec, (const uint8_t*)e->d_state, (long long)e->B, out);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(std::string("k_action_mask launch: ") + hipGetErrorString(err));
+  PROF_END(e, st, MFG_K_ACTION_MASK);
+  return 0;
+}
+extern "C" int mfg_action_mask(mfg_engine* e, uint32_t* out, void* stream) {
+  ENGINE_CALL(e, action_mask_impl(e, out, stream));
+}
+
 // snapshots (checkpoints == fixtures): whole state buffer device<->device, B * layout.size bytes
 static int copy_state(mfg_engine* e, void* dst, const void* src, void* stream) {
   if (!dst || !src) return fail("null argument");

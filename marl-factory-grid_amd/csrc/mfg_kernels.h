@@ -1227,6 +1227,21 @@ __device__ bool door_use_at(const Env& e, int x, int y) {
   wave_sync();
   return true;
 }
+// door_use_at's answer without its write (the action mask, k_action_mask): is a door present in the global pos_dict on
+// a non-wall cell of the 3x3 around (x, y)?
+__device__ bool door_use_valid_at(const Env& e, int x, int y) {
+  SpecP S = e.S;
+  const int W = S->s.W;
+  for (int k = 0; k < 9; k++) {
+    const int px = x + k % 3 - 1, py = y + k / 3 - 1;
+    if (px < 0 || py < 0 || px >= S->s.H || py >= W) continue;
+    const int c = px * W + py;
+    if (S->level[c] == 1) continue;
+    const int d = door_idx(e, c);
+    if (d >= 0 && (uni(e.door()[d]) & DW_PRESENT)) return true;
+  }
+  return false;
+}
 
 template <int NW>
 __device__ void do_action(const Env& e, StepOut<NW>& o, int a, int slot) {
@@ -3757,6 +3772,99 @@ static __global__ void __launch_bounds__(MFG_WPB * 64) MFG_WPE_LOGIC(FULL || MAI
   // (lm: only the maintainer states go back; their paths are read-only here, since a maintainer whose path is used
   // up re-routes in the SEL 2 launch, and C5's 4 x 1,000-cell paths were most of k_logic's writes)
   if constexpr (lm) rec_copy(rec + ms0, e.lds + S->L.o_logic, mlen, e.lane);
+}
+#endif
+
+// The action mask of every env (mfg_action_mask, include/mfg.h): out[env][a] bit s = slot s < n_actions[a] and a step
+// from the record as it stands, with agent a executing slot s before any other agent has acted, would report the
+// action valid (do_action / act_parallel's `valid`, ev_act 0x80 | 1). No built-in rule acts before the agents, so
+// this is a function of the record and the spec alone. One wave per env, the step's own read-only queries on an LDS
+// image of what they read: the step prefix up to the live dirt positions, and the batteries (two coalesced segment
+// copies, as the step stages it). The record is only read and nothing but `out` is written. The time is the chain of
+// wave-uniform queries, one per (agent, slot) with its dependent loads of the level, door and spec tables: C3 has 96
+// of them per env where a step runs 8 actions (903 us against 135 us for k_logic at 65,536 envs; reading
+// the record in place in HBM instead of the image measured the same, 912 us). An agent's Charge / Clean / Item / DoorUse / Dest answers depend on its cell alone, so each is
+// evaluated at most once per agent whatever the number of slots with that opcode; Move once per slot. Counts and cells
+// read from the record are clamped to the spec's capacities, so a record imported with garbage cannot send a load
+// out of the record or the level tables.
+#ifndef MFG_OBS_UNIT  // host-unit kernel (not compiled in the render units)
+template <int NW>
+static __global__ void __launch_bounds__(MFG_WPB * 64) k_action_mask(const MfgDevSpec* S_, const uint8_t* state,
+                                                                      long long B, uint32_t* out) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  SpecP S = (SpecP)S_;
+  const int wid = uni(threadIdx.x >> 6);  // wave-uniform: slice and record addresses become scalar
+  const long long env = (long long)blockIdx.x * (blockDim.x >> 6) + wid;
+  if (env >= B) return;
+  Env e;
+  e.S = S; e.lds = smem + (size_t)wid * S->L.o_logic; e.scratch = nullptr; e.stab = nullptr;
+  e.cmap = nullptr; e.bfs = nullptr; e.hdrp = (int*)(e.lds + S->L.o_hdr); e.lane = lane_id();
+  const int A = S->A, W = S->s.W, HW = S->HW;
+  {  // [0, dirt positions of the live piles) and [batteries), each widened to 16 B: both end inside [0, o_logic)
+    const uint8_t* rec = state + (size_t)env * S->L.size;
+    const int nd0 = min(max(uni(((const int*)(rec + S->L.o_hdr))[H_N_DIRT]), 0), S->dirt_cap);
+    const int end0 = (S->L.o_dirt_pos + 4 * nd0 + 15) & ~15;
+    for (int i = 16 * e.lane; i < end0; i += 16 * MFG_WAVE) *(uint4*)(e.lds + i) = *(const uint4*)(rec + i);
+    const int b1 = S->L.o_battery & ~15, end1 = (S->L.o_battery + 8 * A + 15) & ~15;
+    for (int i = b1 + 16 * e.lane; i < end1; i += 16 * MFG_WAVE) *(uint4*)(e.lds + i) = *(const uint4*)(rec + i);
+    wave_sync();
+  }
+  const bool crashed = e.H(H_CRASHED) != 0;  // a crashed env reports done and runs no action (env_step)
+  const int n_items = min(e.H(H_N_ITEMS), S->imax), n_pods = min(e.H(H_N_PODS), S->pmax);
+  const int n_drops = min(e.H(H_N_DROPS), S->dropmax), n_dirt = min(e.H(H_N_DIRT), S->dirt_cap);
+  uint32_t my[NW];
+#pragma unroll
+  for (int h = 0; h < NW; h++) my[h] = 0;
+  for (int a = 0; a < A && !crashed; a++) {
+    if (uni(e.agpar()[a])) continue;  // a paralysed agent's action is skipped: no bit
+    const int pos = uni(e.agpos()[a]);
+    const bool placed = pos >= 0 && pos < HW;
+    const int x = placed ? pos / W : 0, y = placed ? pos - x * W : 0;
+    const int n = min(S->s.n_actions[a], MFG_MAX_ACTIONS);
+    uint32_t bits = 0, known = 0, memo = 0;  // per opcode: answered already, and the answer
+    for (int s = 0; s < n; s++) {
+      const CS mfg_action& ac = action_of(e, a, s);
+      const int op = ac.op;
+      bool v = false;
+      if (op == MFG_ACT_NOOP) {
+        v = true;
+      } else if (!placed || op < 0 || op > MFG_ACT_MACHINE) {
+        v = false;
+      } else if (op == MFG_ACT_MOVE) {  // do_action: pos != t && !blocked && level[t] != 1 && !blocking_others
+        static const int DX[8] = {-1, -1, 0, 1, 1, 1, 0, -1};
+        static const int DY[8] = {0, 1, 1, 1, 0, -1, -1, -1};
+        const int nx = x + DX[ac.arg & 7], ny = y + DY[ac.arg & 7];
+        if (nx >= 0 && ny >= 0 && nx < S->s.H && ny < W) {  // (levels are wall-bounded: always, from a floor cell)
+          const int t = nx * W + ny;
+          v = t != pos && !blocked_at<NW>(e, t) && S->level[t] != 1;
+          if (v && S->s.agent_blocking[a]) v = colliders_at<NW>(e, t) == 0;  // is_occupied
+        }
+      } else if ((known >> op) & 1) {
+        v = (memo >> op) & 1;
+      } else {
+        if (op == MFG_ACT_DOORUSE) {
+          v = door_use_valid_at(e, x, y);
+        } else if (op == MFG_ACT_ITEM) {  // a drop-off on the cell: the drop-off branch, never valid (Q8)
+          v = grp_first_g<NW>(e.drops(), n_drops, pos, EW_ALIVE, e.lane) < 0 &&
+              grp_first_g<NW>(e.items(), n_items, pos, EW_ALIVE, e.lane) >= 0;
+        } else if (op == MFG_ACT_CHARGE) {
+          v = grp_first_g<NW>(e.pods(), n_pods, pos, EW_ALIVE, e.lane) >= 0 && !(e.bat()[a] >= 1.0) &&
+              agents_count_at<NW>(e, pos) <= 1;
+        } else if (op == MFG_ACT_CLEAN) {
+          v = grp_first(e.dirtpos(), n_dirt, pos, EW_PRESENT, e.lane) >= 0;
+        }  // MFG_ACT_DEST: fails off a destination and crashes on one (Q17); MFG_ACT_MACHINE: reported invalid (Q18)
+        known |= 1u << op;
+        memo |= (v ? 1u : 0u) << op;
+      }
+      bits |= (v ? 1u : 0u) << s;
+    }
+    agent_set(my, a, e.lane, bits);
+  }
+#pragma unroll
+  for (int h = 0; h < NW; h++) {
+    const int a = h * MFG_WAVE + e.lane;
+    if (a < A) out[(size_t)env * A + a] = my[h];
+  }
 }
 #endif
 

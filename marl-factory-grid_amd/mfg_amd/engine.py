@@ -15,7 +15,8 @@ from . import abi
 LIB_PATH = Path(os.environ.get('MFG_HIP_LIB') or Path(__file__).resolve().parent / '_lib' / 'libmfg_hip.so')
 EV_MISC = abi.EV_MISC_N  # MFG_EV_MISC_N (include/mfg.h)
 HDR_N = 40  # MFG_HDR_N (csrc/mfg_device.h)
-KERNELS = ['k_logic', 'k_resetdone', 'k_obs', 'k_replay', 'k_reset', 'k_obs_done', 'k_replay_sel']  # MFG_K_* ids (include/mfg.h)
+KERNELS = ['k_logic', 'k_resetdone', 'k_obs', 'k_replay', 'k_reset', 'k_obs_done', 'k_replay_sel',
+           'k_action_mask']  # MFG_K_* ids (include/mfg.h)
 
 LAYOUT_KEYS = ['size', 'o_hdr', 'o_rule_ctr', 'o_agent_pos', 'o_agent_arr', 'o_agent_par', 'o_frozen_org',
                'o_frozen_gp', 'o_door', 'o_items', 'o_pods', 'o_drops', 'o_dests', 'o_dirt_pos', 'o_dirt_id',
@@ -61,6 +62,8 @@ def load_lib():
     L.mfg_step.restype = C.c_int
     L.mfg_replay.argtypes = [C.c_void_p, C.c_void_p]
     L.mfg_replay.restype = C.c_int
+    L.mfg_action_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mfg_action_mask.restype = C.c_int
     L.mfg_export_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.mfg_export_state.restype = C.c_int
     L.mfg_import_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -204,6 +207,19 @@ class Engine:
                                _ptr(ev_watch), _ptr(ev_misc), int(bool(auto_reset)) | (2 if defer_replay else 0),
                                self._stream()), 'mfg_step',
                self.h)
+
+    def action_mask(self, out=None):
+        """The action mask of every env from its state as it stands (mfg_action_mask, include/mfg.h): int32 [B, A]
+        carrying the 32-bit pattern, bit s = agent a's slot s would be valid if it acted now, before any other
+        agent. One read-only kernel on the current stream, no sync; out: a contiguous int32 [B, A] tensor to fill."""
+        torch = self.torch
+        if out is None:
+            out = torch.empty((self.B, self.A), dtype=torch.int32, device=self.device)
+        elif (out.dtype != torch.int32 or tuple(out.shape) != (self.B, self.A) or not out.is_contiguous()
+              or out.device != self.device):
+            raise ValueError(f'out must be a contiguous int32 tensor [{self.B}, {self.A}] on {self.device}')
+        _check(self.L.mfg_action_mask(self.h, _ptr(out), self._stream()), 'mfg_action_mask', self.h)
+        return out
 
     def profile(self, enable=True):
         """Record HIP events around every kernel launch (on the launch stream) while enabled."""

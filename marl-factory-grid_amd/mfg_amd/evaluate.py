@@ -24,6 +24,7 @@ from pathlib import Path
 import torch
 
 from . import learn_lib
+from .action_mask import masked_logits
 from .marl import RecurrentAC
 from .seac import AgentNets
 
@@ -79,21 +80,27 @@ def act_supported(e_dim, ae_dim, hd, n_max):
 
 
 def policy_act(w, emb, emb_strides, n_envs, n_agents, n_act, prev_action, prev_done, h, h_strides, u, act_out,
-               logits_out=None, greedy=False, check=False):
+               logits_out=None, greedy=False, check=False, mask=None):
     """One ``mfg_policy_act`` call on the current stream. w: ``actor_weights``; emb / h: f32 device tensors read at
     env * strides[0] + agent * strides[1] (elements); n_act i32 [g] on the device; prev_action / prev_done None: an
-    episode start. Returns the kernel's return code (-1: sizes outside its limits, nothing launched), or with ``check``
-    raises on it."""
+    episode start. mask: the action-mask words, int32 [n_envs, n_agents] on the device (``Engine.action_mask``): the
+    call is ``mfg_policy_act_masked`` and an action whose bit is clear is never picked. Returns the kernel's return code
+    (-1: sizes outside its limits, nothing launched), or with ``check`` raises on it."""
     g, k_in, e_dim = w['w1t'].shape
     hd, n_max = w['wbt'].shape[1:]
     ptr = learn_lib.ptr
     args = (emb.data_ptr(), emb_strides[0], emb_strides[1], n_envs, n_agents, g, e_dim, k_in - e_dim, hd, n_max,
             ctypes.byref(_weights_struct(w)), n_act.data_ptr(), ptr(prev_action), ptr(prev_done), h.data_ptr(),
-            h_strides[0], h_strides[1], ptr(u), 1 if greedy else 0, act_out.data_ptr(), ptr(logits_out),
-            learn_lib.stream(emb.device))
+            h_strides[0], h_strides[1], ptr(u), 1 if greedy else 0)
+    name = 'mfg_policy_act'
+    if mask is not None:
+        if mask.dtype != torch.int32 or mask.numel() != n_envs * n_agents or not mask.is_contiguous():
+            raise ValueError(f'mask must be a contiguous int32 tensor [{n_envs}, {n_agents}]')
+        name, args = 'mfg_policy_act_masked', args + (mask.data_ptr(),)
+    args += (act_out.data_ptr(), ptr(logits_out), learn_lib.stream(emb.device))
     if check:
-        return learn_lib.call('mfg_policy_act', *args)
-    return learn_lib.lib().mfg_policy_act(*args)
+        return learn_lib.call(name, *args)
+    return getattr(learn_lib.lib(), name)(*args)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -117,10 +124,14 @@ def actor_step(policy, emb, a_in, h):
     return out['logits'][:, :, 0], out['hidden_actor'][:, :, 0]
 
 
-def sample_inversion(logits, u, n_act=None):
+def sample_inversion(logits, u, n_act=None, mask=None):
     """``mfg_sample_categorical`` in tensor code: the action whose CDF bin holds u * sum(exp(l - max)) over the first
-    n_act columns (all by default); the last action when rounding passes the last bin; -1 for non-finite logits."""
+    n_act columns (all by default); the last action when rounding passes the last bin; -1 for non-finite logits.
+    mask: action-mask words, int32 of u's shape: a logit whose bit is clear counts as -inf; a row whose word has no
+    bit set among its columns is sampled unmasked (``mfg_policy_act_masked``'s rule)."""
     lg = logits if n_act is None else logits[..., :n_act]
+    if mask is not None:
+        lg = masked_logits(lg, mask)
     ex = torch.exp(lg - lg.max(-1, keepdim=True).values)
     cdf = torch.cumsum(ex, -1)
     s = cdf[..., -1]
@@ -168,12 +179,15 @@ class BatchedEvaluator:
     greedy: argmax instead of sampling. generator: draws the sampling uniforms (default: the device's global one).
     record: keep every step's actions, rewards and dones (``actions`` [steps, B, A] i32, ``rewards`` f64, ``dones``
     [steps, B] u8 after ``run``). poll_every: steps between two reads of the finished-env counter (the only host sync).
+    mask_invalid: every step takes the engine's action mask (``Engine.action_mask``, one more kernel) and acts masked, on
+    both paths: an action that would be invalid if the agent acted first is never picked, unless none of the agent's
+    actions is valid (a crashed env, a paralysed agent), which acts unmasked.
 
     After ``run``: ``rows`` f32 [B, n_episodes, A + 1] (per episode the agents' reward sums, then their f32 sum),
     ``lengths`` i32 [B, n_episodes], ``steps``; ``frame(env=b)`` is the reference's melted frame of env b."""
 
     def __init__(self, factory, policy, n_episodes, fused=None, greedy=False, generator=None, record=False,
-                 poll_every=None, cap=32, check_cap=True):
+                 poll_every=None, cap=32, check_cap=True, mask_invalid=False):
         from .engine import PackedObs
         self.f = factory
         eng = factory.engine
@@ -196,6 +210,8 @@ class BatchedEvaluator:
         self.E = net.obs_proj.weight.shape[0] if self.shared else net.obs_emb_size
         self.H = net.hidden_size_actor
         self.greedy, self.gen, self.record = bool(greedy), generator, bool(record)
+        self.mask_invalid = bool(mask_invalid)
+        self.mask = torch.zeros((self.B, self.A), dtype=torch.int32, device=self.dev) if self.mask_invalid else None
         self.poll_every = max(1, int(poll_every)) if poll_every is not None else 16
         if fused is None:  # measured (profiles/eval.json): fused 1.25-1.44x with AgentNets, 0.88-1.04x with a shared net
             fused = not self.shared
@@ -268,13 +284,15 @@ class BatchedEvaluator:
         if not self.shared:
             self._project()
         u = self._uniforms()
+        mask = self.f.engine.action_mask(out=self.mask) if self.mask_invalid else None
         if self.fused:
             if self.shared:
                 emb, es, hs = self.pobs.emb, (A * self.E, self.E), (A * self.H, self.H)
             else:
                 emb, es, hs = self._emb, (self.E, B * self.E), (self.H, B * self.H)
             policy_act(self.w, emb, es, B, A, self.n_act_dev, None if first else self.act,
-                       None if first else self.done, self.h, hs, u, self.act, logits_out, self.greedy, check=True)
+                       None if first else self.done, self.h, hs, u, self.act, logits_out, self.greedy, check=True,
+                       mask=mask)
             return
         keep = torch.zeros(B, dtype=torch.bool, device=self.dev) if first else ~self.done.bool()
         a_in = torch.where(keep[:, None], self.act.long(), torch.full_like(self.act, -1, dtype=torch.long))
@@ -298,16 +316,22 @@ class BatchedEvaluator:
             logits = logits.transpose(0, 1)  # [B, A, n_max]
         if logits_out is not None:
             logits_out[..., :logits.shape[-1]].copy_(logits)
-        self._pick(logits.contiguous(), u)
+        self._pick(logits.contiguous(), u, mask)
 
-    def _pick(self, logits, u):
-        """Actions from logits [B, A, n] (engine order) into ``act``."""
+    def _pick(self, logits, u, mask=None):
+        """Actions from logits [B, A, n] (engine order) into ``act``; mask: action-mask words [B, A] or None."""
         uniform = len(set(self.n_act)) == 1
+        groups = [(0, self.A, self.n_act[0])] if uniform else [(i, i + 1, c) for i, c in enumerate(self.n_act)]
+        if mask is not None:  # the raw logits decide whether a row is a distribution; the filled ones, what is picked
+            raw, logits = logits, logits.clone()
+            for lo, hi, n in groups:
+                logits[:, lo:hi, :n] = masked_logits(raw[:, lo:hi, :n], mask[:, lo:hi])
         if self.greedy:
-            for lo, hi, n in ([(0, self.A, self.n_act[0])] if uniform else [(i, i + 1, c) for i, c in enumerate(self.n_act)]):
+            for lo, hi, n in groups:
                 lg = logits[:, lo:hi, :n]
                 a = lg.argmax(-1).to(torch.int32)
-                self.act[:, lo:hi] = torch.where(torch.isfinite(lg).all(-1), a, torch.full_like(a, -1))
+                ok = torch.isfinite(lg if mask is None else raw[:, lo:hi, :n]).all(-1)
+                self.act[:, lo:hi] = torch.where(ok, a, torch.full_like(a, -1))
             return
         if logits.is_cuda and uniform:
             learn_lib.call('mfg_sample_categorical', logits.data_ptr(), logits.shape[-1], self.n_act[0], u.data_ptr(),

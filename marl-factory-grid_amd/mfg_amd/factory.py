@@ -19,6 +19,7 @@ import random as _pyrandom
 import numpy as np
 
 from . import abi
+from .action_mask import agent_masks, dense_mask
 from .engine import Engine, PackedObs, RecordView, events_from_rows, EV_MISC, HDR, HDR_N
 from .host_rules import HostRules, StaleStateError, StateView, fold_step, level_map, pre_snapshot
 from .info import rebuild_info
@@ -212,6 +213,12 @@ class Factory:
         self._last = (reward, done, info)
         return None, self._obs_list(), reward, done, info
 
+    def action_mask(self):
+        """Which actions would be valid if the agent acted now, before any other agent (mfg_action_mask, include/mfg.h):
+        a list with one numpy bool array of length n_actions[a] per agent. Exact for the first agent of a step; an
+        earlier agent of the same step can still invalidate a later one's action (a door it toggles)."""
+        return agent_masks(self._eng.action_mask()[0].cpu().numpy(), self.spec.n_actions)
+
     # ---- entity views (factory.py:131-132, 262-292) ----
     def snapshot(self):
         """The env's state as a `views.Snapshot` (one device->host copy of the record)."""
@@ -380,6 +387,16 @@ class BatchedFactory:
                          ev_watch=self.ev_watch, ev_misc=self.ev_misc, auto_reset=True, step_base=self.t)
         self.t += 1
         return self.obs, self.reward, self.done, (self.ev_act, self.ev_watch, self.ev_misc)
+
+    def action_mask(self, dense=False):
+        """The envs' action masks for the next step (mfg_action_mask, include/mfg.h), from their state as it stands
+        (after a step with auto-reset: the new episode's). int32 [B, A] words, bit s = agent a's slot s would be valid
+        if it acted first; dense=True: a bool tensor [B, A, max n_actions] (columns past an agent's count are False).
+        One read-only kernel, no host sync."""
+        if not self._created:
+            raise RuntimeError('call reset() first')
+        words = self.engine.action_mask()
+        return dense_mask(words, max(self.spec.n_actions)) if dense else words
 
     def rollout(self, K, philox_seed, obs=None, reward=None, done=None):
         """K steps with on-device Philox synthetic actions into caller buffers [K, ...] (any may be None)."""

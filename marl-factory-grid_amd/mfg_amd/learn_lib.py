@@ -26,6 +26,12 @@ ARGTYPES = {
     'mfg_eval_fold': [_p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p],
 }
 
+# include/mfg_act.h, bound the same way
+ACT_ARGTYPES = {
+    'mfg_policy_act_masked': [_p, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _i64, _i64,
+                              _p, _i32, _p, _p, _p, _p],
+}
+
 ACTOR_FIELDS = ('action_emb', 'w1t', 'b1', 'w3t', 'b3', 'wiht', 'bih', 'whht', 'bhh', 'wat', 'ba', 'wbt', 'bb')
 
 
@@ -38,12 +44,12 @@ _LIB = None
 
 
 def lib():
-    """libmfg_hip.so with every function of include/mfg_learn.h bound (once)."""
+    """libmfg_hip.so with every function of include/mfg_learn.h and include/mfg_act.h bound (once)."""
     global _LIB
     if _LIB is None:
         from .engine import load_lib
         L = load_lib()
-        for name, argtypes in ARGTYPES.items():
+        for name, argtypes in {**ARGTYPES, **ACT_ARGTYPES}.items():
             fn = getattr(L, name)  # a library without the function is an error here, not at its first use
             fn.argtypes, fn.restype = argtypes, C.c_int
         _LIB = L

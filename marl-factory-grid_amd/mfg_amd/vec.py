@@ -36,9 +36,13 @@ class VectorFactory:
 
     metadata = {'autoreset_mode': 'same-step'}
 
-    def __init__(self, config_file, num_envs, *, device=0, seed_base=0, obs_dtype='float32', env=None):
+    def __init__(self, config_file, num_envs, *, device=0, seed_base=0, obs_dtype='float32', env=None,
+                 action_mask=False):
+        """action_mask: `reset` and `step` put the next step's action masks into infos['action_mask'] (int32 words
+        [B, A], `BatchedFactory.action_mask`; one more kernel per step)."""
         self.env = env if env is not None else BatchedFactory(config_file, num_envs, device=device,
                                                                 seed_base=seed_base, obs_dtype=obs_dtype)
+        self.with_action_mask = bool(action_mask)
         self.torch = self.env.torch
         self.spec = self.env.spec
         self.num_envs = self.env.B
@@ -69,7 +73,7 @@ class VectorFactory:
             keep = (m == 0)
             self._ret.mul_(keep.unsqueeze(1).to(self._ret.dtype))
             self._len.mul_(keep.to(self._len.dtype))
-        return obs, {}
+        return obs, ({'action_mask': self.env.action_mask()} if self.with_action_mask else {})
 
     def step(self, actions):
         obs, rew, done, (_, _, ev_misc) = self.env.step(actions)
@@ -86,6 +90,8 @@ class VectorFactory:
                  '_final': done_b.clone()}
         self._ret.masked_fill_(done_b.unsqueeze(1), 0.0)
         self._len.masked_fill_(done_b, 0)
+        if self.with_action_mask:  # of the state the next actions meet (a finished env: its new episode's)
+            infos['action_mask'] = self.env.action_mask()
         return obs, rew, term, trunc, infos
 
     def close(self):
@@ -97,10 +103,13 @@ class ParallelFactory:
 
     metadata = {'render_modes': ['human', 'ansi', 'rgb_array'], 'name': 'marl_factory_grid_amd'}
 
-    def __init__(self, config_file, *, device=0, py_seed=0, render_mode=None):
+    def __init__(self, config_file, *, device=0, py_seed=0, render_mode=None, action_mask=False, env=None):
+        """action_mask: `reset` and `step` put each agent's mask for the next step into infos[agent]['action_mask']
+        (a numpy bool array of its action count, `Factory.action_mask`). env: a ready `Factory` to wrap."""
         self._cfg, self._device, self._seed = config_file, device, int(py_seed)
         self.render_mode = render_mode
-        self.env = Factory(config_file, device=device, py_seed=self._seed)
+        self.with_action_mask = bool(action_mask)
+        self.env = env if env is not None else Factory(config_file, device=device, py_seed=self._seed)
         self.spec = self.env.spec
         self.possible_agents = [f'Agent[{n}]' for n in self.spec.agent_names]
         self.agents = []
@@ -122,7 +131,11 @@ class ParallelFactory:
             self.env = Factory(self._cfg, device=self._device, py_seed=self._seed)
         obs = self.env.reset()
         self.agents = list(self.possible_agents)
-        return dict(obs), {a: {} for a in self.agents}
+        infos = {a: {} for a in self.agents}
+        if self.with_action_mask:
+            for a, m in zip(self.possible_agents, self.env.action_mask()):
+                infos[a]['action_mask'] = m
+        return dict(obs), infos
 
     def step(self, actions):
         acts = [int(actions[a]) for a in self.possible_agents]
@@ -133,6 +146,9 @@ class ParallelFactory:
         out = ({a: o for a, o in zip(names, obs)}, {a: r for a, r in zip(names, rew)},
                {a: bool(done and not trunc) for a in names}, {a: bool(trunc) for a in names},
                {a: dict(info) for a in names})
+        if self.with_action_mask and not done:
+            for a, m in zip(names, self.env.action_mask()):
+                out[4][a]['action_mask'] = m
         if done:
             self.agents = []
         return out
@@ -169,6 +185,13 @@ class SB3VecFactory:
     def reset(self):
         obs, _ = self.venv.reset()
         return self._np_obs(obs)
+
+    def action_masks(self):
+        """The next step's action masks in sb3-contrib's MaskablePPO convention for a MultiDiscrete action space: bool
+        [B, sum(n_actions)], the agents' masks side by side (`BatchedFactory.action_mask`; one kernel, one copy)."""
+        spec = self.venv.spec
+        dense = self.venv.env.action_mask(dense=True).cpu().numpy()
+        return np.concatenate([dense[:, a, :n] for a, n in enumerate(spec.n_actions)], axis=1)
 
     def step_async(self, actions):
         self._actions = np.asarray(actions, dtype=np.int32).reshape(self.num_envs, -1)
