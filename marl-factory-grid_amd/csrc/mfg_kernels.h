@@ -1606,8 +1606,8 @@ __device__ __forceinline__ void bfs_sync() {
 // candidates (fringe index i, adjacency slot k) of a level in (i, k) order; here every lane expands fringe
 // nodes and the order is recovered from keys i*8+k: the meeting point is the smallest key whose neighbour
 // is in the other tree, a node's parent is its smallest discovering key (LDS atomicMin), and the new fringe
-// is the discoveries compacted in key order. Route (floor indices) into `route`, returns its length or -1
-// (NodeNotFound / NetworkXNoPath / longer than cap: a crash upstream, or engine capacity).
+// is the discoveries compacted in key order. Route (floor indices) into `route`, returns its length, -1
+// (NodeNotFound / NetworkXNoPath: a crash upstream) or -2 (a route was found but is longer than cap: engine capacity).
 __device__ int bfs_route(const Env& e, int src, int dst, uint16_t* route, int cap) {
   SpecP S = e.S;
   const int nf = S->nf, lane = e.lane;
@@ -1718,7 +1718,7 @@ __device__ int bfs_route(const Env& e, int src, int dst, uint16_t* route, int ca
       k = n;
       for (int w = succ[meet]; w != BFS_ROOT; w = succ[w]) route[k++] = (uint16_t)w;
     } else {
-      len = -1;
+      len = -2;
     }
   }
   len = rl(len, 0);
@@ -1739,7 +1739,10 @@ __device__ bool maint_route(const Env& e, int k, int target_cell, int* crashed) 
     wave_sync();
   }
   const int n = bfs_route(e, S->cell_f[pos], S->cell_f[target_cell], route, S->path_cap + 1);
-  if (n < 0) { *crashed = 2; return false; }  // NodeNotFound / NetworkXNoPath (or route > path_cap)
+  if (n < 0) {  // NodeNotFound / NetworkXNoPath upstream; a route over path_cap is the engine's limit, not a reference crash
+    *crashed = n == -2 ? MFG_CRASH_CAPACITY : MFG_CRASH_ROUTE;
+    return false;
+  }
   uint16_t* path = e.mpath(k);
   for (int i = e.lane; i < n - 1; i += MFG_WAVE) path[i] = (uint16_t)S->floor_init[route[i + 1]];
   wave_sync();
@@ -1868,30 +1871,51 @@ __device__ void rule_tick_step(const Env& e, StepOut<NW>& o, int ri, int* scratc
   } else if (op == MFG_RULE_RESPAWN_ITEMS) {  // items/rules.py:28-33
     int c = uni(e.rctr()[ri]);
     if (!c) {
-      if (S->s.items_quantity - e.H(H_N_ITEMS) > 0) o.crashed = 1;  // Item(pos, n, freq) TypeError upstream
+      if (S->s.items_quantity - e.H(H_N_ITEMS) > 0) {  // Item(pos, n, freq) TypeError upstream, raised after
+        e.setH(H_DEBT, e.H(H_DEBT) + 1);                //  trigger_spawn drew its free positions (one floor shuffle)
+        o.crashed = MFG_CRASH_RULE;
+      }
     } else {
       wave_sync();
       if (e.lane == 0) e.rctr()[ri] = c - 1 > 0 ? c - 1 : 0;
       wave_sync();
     }
   } else if (op == MFG_RULE_BATTERY_DECHARGE || op == MFG_RULE_DONE_BATTERY) {  // batteries/rules.py:50-64
-    bool missing = false;
+    bool missing = false, miss[NW];
+    double old_b[NW];
 #pragma unroll
     for (int h = 0; h < NW; h++) {
       const int a = h * MFG_WAVE + e.lane;
+      miss[h] = false;
+      old_b[h] = 0.0;
       if (a < S->A) {
         double cost = ru.f[0];
         if (ru.i[2])  // per_action_costs[agent.state.identifier]: the executed action's class, 'Noop' if paralyzed
           cost = o.my_slot[h] >= 0 ? S->s.actions[a][o.my_slot[h]].battery_cost : (ru.i[3] ? ru.f[3] : __builtin_nan(""));
-        missing |= cost != cost;
+        miss[h] = cost != cost;
+        missing |= miss[h];
         double b = e.bat()[a];
+        old_b[h] = b;
         if (b != 0.0 && cost == cost) {
           double nv = cost + b;
           e.bat()[a] = nv > 0.0 ? nv : 0.0;
         }
       }
     }
-    if (ballot(missing)) o.crashed = MFG_CRASH_RULE;  // KeyError upstream
+    if (ballot(missing)) {  // KeyError upstream: the rule's loop over the agents ends at the first one without a cost,
+      int first = S->A;     // so the agents after it keep their charge (the next reset freezes it into the obs)
+#pragma unroll
+      for (int h = NW - 1; h >= 0; h--) {
+        const u64 m = ballot(miss[h]);
+        if (m) first = h * MFG_WAVE + ffs64(m);
+      }
+#pragma unroll
+      for (int h = 0; h < NW; h++) {
+        const int a = h * MFG_WAVE + e.lane;
+        if (a < S->A && a > first) e.bat()[a] = old_b[h];
+      }
+      o.crashed = MFG_CRASH_RULE;
+    }
     wave_sync();
   } else if (op == MFG_RULE_RESPAWN_DIRT) {  // clean_up/rules.py:49-59
     int c = uni(e.rctr()[ri]);
@@ -1967,7 +1991,11 @@ __device__ void rule_post_step(const Env& e, StepOut<NW>& o, int ri) {
   if (op == MFG_RULE_RESPAWN_ITEMS) {  // items/rules.py:35-43
     int c = uni(e.rctr()[ri]);
     if (!c) {
-      if (S->s.items_quantity - e.H(H_N_ITEMS) > 0) { o.crashed = 1; return; }
+      if (S->s.items_quantity - e.H(H_N_ITEMS) > 0) {  // as in rule_tick_step: one floor shuffle, then the TypeError
+        e.setH(H_DEBT, e.H(H_DEBT) + 1);
+        o.crashed = MFG_CRASH_RULE;
+        return;
+      }
       o.respawn_items_value = S->s.items_quantity;
     } else {
       wave_sync();

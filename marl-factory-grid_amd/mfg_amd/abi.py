@@ -44,7 +44,8 @@ EV_MISC_N = 16
 EVM_DOOR_COLS = (EVM_DOOR_COLL_LO, EVM_DOOR_COLL_HI, EVM_DOOR_COLL_2, EVM_DOOR_COLL_3)
 EVM_MAINT_COLS = (EVM_MAINT_COLL, EVM_MAINT_COLL_HI)
 # crash reasons (MFG_CRASH_*)
-CRASH_NAMES = {0: 'none', 1: 'reference crash path (DestAction on a destination Q17 / RespawnItems Q9)',
+CRASH_NAMES = {0: 'none', 1: 'rule or reset crash path (DestAction on a destination Q17, RespawnItems Q9, a missing '
+                           'per-action battery cost, an exception inside reset)',
                2: 'maintainer route: no path', 3: 'maintainer: no free cell', 4: 'maintainer: empty target list',
                5: 'maintainer: empty path', 6: 'maintainer: step not in MOVEMAP', 7: 'engine capacity exceeded',
                8: 'action index out of range'}

@@ -29,6 +29,18 @@ from . import views as _views
 INIT_CREATE, INIT_KEEP_MT, INIT_NO_RESET = 1, 2, 4  # include/mfg.h MFG_INIT_*
 
 
+def crash_message(reason):
+    """What Factory.step raises for a crashed step: the reason by name; 'the reference crashes here' only for the
+    reference's own crash paths (MFG_CRASH_RULE .. MFG_CRASH_MOVE), 'engine capacity' for MFG_CRASH_CAPACITY."""
+    name = abi.CRASH_NAMES.get(int(reason), f'unknown reason {int(reason)}')
+    if 1 <= int(reason) <= 6:
+        return f'the reference crashes on this step: {name} (reason {int(reason)}); env state is flagged'
+    if int(reason) == 7:
+        return (f'engine capacity exceeded on this step (reason 7: dirt slots, identifier pairs, the reach counter or '
+                f'a maintainer route longer than the stored path); the reference keeps running here; env state is flagged')
+    return f'this step crashed: {name} (reason {int(reason)}); env state is flagged'
+
+
 class _Discrete:
     """Minimal stand-in for gymnasium.spaces.Discrete when gymnasium is not installed."""
 
@@ -195,7 +207,7 @@ class Factory:
         ev_a, ev_w = self._ev_a[0].cpu().numpy(), self._ev_w[0].cpu().numpy()
         ev = events_from_rows(ev_a, ev_w, self._ev_m[0].cpu().numpy())
         if ev['crashed']:
-            raise RuntimeError('the reference crashes on this step (SURVEY App. A Q9/Q17); env state is flagged')
+            raise RuntimeError(crash_message(ev['crash_reason']))
         reward = [float(x) for x in self._rew[0].cpu().numpy()]
         done = bool(self._done.item())
         self._step = ev['step']

@@ -59,6 +59,9 @@ def lib():
         L.oracle_posdict.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         for fn in ('oracle_floor', 'oracle_keyrank', 'oracle_mt', 'oracle_pcg'):
             getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p]
+        for fn in ('oracle_maint_path_len', 'oracle_maint_route_len'):
+            getattr(L, fn).argtypes = [C.c_void_p, C.c_int]
+            getattr(L, fn).restype = C.c_int
         L.oracle_mt_u32_seq.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.oracle_mt_shuffle_range.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.oracle_pcg_seq.argtypes = [C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double]
@@ -183,6 +186,14 @@ class OracleEnv:
         out = np.zeros(4, np.uint64)
         self.L.oracle_pcg(self.h, _p(out))
         return out
+
+    def maint_path_len(self, k):
+        """Cells left on maintainer k's current route (the reference's len(maintainer._path))."""
+        return int(self.L.oracle_maint_path_len(self.h, k))
+
+    def maint_route_len(self, k):
+        """Cells of maintainer k's path as calculate_route last stored it (len(route) - 1)."""
+        return int(self.L.oracle_maint_route_len(self.h, k))
 
     def results(self):
         buf = (Res * 4096)()

@@ -6,6 +6,7 @@
 import numpy as np
 import pytest
 
+import crash_cases as CC
 import golden_compare as G
 
 UNITS = np.load(G.GOLDEN / 'units.npz')
@@ -18,7 +19,10 @@ FIXTURES = [('large8', 'large8.yaml'), ('rooms4', 'rooms4.yaml'), ('simple1', 's
             ('clean_and_bring', 'clean_and_bring.yaml'), ('large_full', 'large_full.yaml'),
             ('grid128_r10', 'grid128_r10.yaml'), ('qquad_full', 'qquad_full.yaml'), ('grid128_r20', 'grid128_r20.yaml'),
             ('grid128_full', 'grid128_full.yaml'), ('wide40', 'wide40.yaml'),
-            ('qquad_doors', 'qquad_doors.yaml'), ('agents81', 'agents81.yaml')]
+            ('qquad_doors', 'qquad_doors.yaml'), ('agents81', 'agents81.yaml'),
+            # the crash configs (crash_cases.py) and the serpentine, whose routes of several hundred nodes pin the
+            # oracle's bidirectional search (the engine stops at its stored-path limit there: test_gpu_crash_paths.py)
+            *CC.FIXTURES, ('serpentine41', 'serpentine41.yaml')]
 
 
 def test_mt19937_matches_cpython():
@@ -67,12 +71,18 @@ def test_oracle_replays_reference_fixture(tag, cfg, seed):
         t, st = r['t'], r['step']
         if st == 0:
             obs = env.reset()
+            if r.get('reset_crashed'):  # the reference raised inside reset(): the record ends the run
+                rew, done, ev = env.step([0] * spec.n_agents)
+                assert ev.crashed and done and ev.crash_reason == CC.RULE, (t, ev.crashed, ev.crash_reason)
+                break
         else:
             rew, done, ev = env.step(r['actions'])
             obs = env.obs_list()
             if r.get('crashed'):
-                assert ev.crashed
+                want = CC.expected_reason(r['crashed'], r.get('crash_site'))
+                assert ev.crashed and done and ev.crash_reason == want, (t, r['crashed'], ev.crash_reason, want)
                 continue
+            assert not ev.crashed, (t, 'the oracle crashed where the reference did not', ev.crash_reason)
             if [float(x) for x in rew] != r['reward']:
                 errs.append((t, 'reward'))
             # the host replay of the Result list (custom host rules merge into it) folds to the same f64 rewards

@@ -19,6 +19,7 @@ import json
 import os
 import random
 import sys
+import traceback
 from pathlib import Path
 
 import numpy as np
@@ -108,14 +109,19 @@ def run(cfg_name, py_seed, n_steps, action_seed, full_obs_every, level_path=None
     random.seed(py_seed)
     Object._u_idx.clear()
     sink = io.StringIO()
+    reset_crashed = None
     with contextlib.redirect_stdout(sink):
         env = Factory(str(cfg), custom_level_path=level_path)
-        obs = env.reset()
+        try:
+            obs = env.reset()
+        except Exception as ex:  # reference crash paths inside reset(): record and end the run
+            reset_crashed = f'{type(ex).__name__}: {ex}'
     H, W = env.map.level_shape
     arng = np.random.default_rng(action_seed)
-    n_act = [len(a.actions) for a in _group(env, 'Agent')]
+    agents = _group(env, 'Agent') or []
+    n_act = [len(a.actions) for a in agents]
     rec = dict(config=cfg_name, py_seed=py_seed, action_seed=action_seed, H=H, W=W,
-               agent_names=[a.name for a in _group(env, 'Agent')], n_actions=n_act,
+               agent_names=[a.name for a in agents], n_actions=n_act,
                named_action_space=env.named_action_space,
                obs_layers={k: list(v) for k, v in env.obs_builder.obs_layers.items()},
                steps=[])
@@ -149,6 +155,9 @@ def run(cfg_name, py_seed, n_steps, action_seed, full_obs_every, level_path=None
             obs_full[f't{t_global}'] = o
 
     episode, step = 0, 0
+    if reset_crashed:  # no state to snapshot: the record carries the exception alone
+        rec['steps'].append(dict(t=0, episode=0, step=0, reset_crashed=reset_crashed))
+        return rec, obs_full, floor_at_reset, keyorder_at_reset
     floor_at_reset['e0'] = floor_arr(env, W)
     keyorder_at_reset['e0'] = np.asarray(cell_keys(), dtype=np.int32)
     record(0, 0, 0, None, None, False, None, list(obs.values()))
@@ -157,20 +166,28 @@ def run(cfg_name, py_seed, n_steps, action_seed, full_obs_every, level_path=None
         t += 1
         step += 1
         acts = [int(arng.integers(0, n)) for n in n_act]
-        crashed = None
+        crashed = crash_site = None
         with contextlib.redirect_stdout(sink):
             try:
                 _, o, r, d, info = env.step(acts)
             except Exception as ex:  # reference crash paths: record and end the episode
                 crashed = f'{type(ex).__name__}: {ex}'
+                crash_site = traceback.extract_tb(ex.__traceback__)[-1].name  # the function that raised
                 o, r, d, info = [], None, True, None
         info = None if info is None else {k: float(v) for k, v in info.items()}
         record(t, episode, step, acts, None if r is None else [float(x) for x in r], bool(d), info, o, crashed)
+        if crashed:
+            rec['steps'][-1]['crash_site'] = crash_site
         if d:
             episode += 1
             step = 0
             with contextlib.redirect_stdout(sink):
-                obs = env.reset()
+                try:
+                    obs = env.reset()
+                except Exception as ex:
+                    rec['steps'].append(dict(t=t, episode=episode, step=0,
+                                             reset_crashed=f'{type(ex).__name__}: {ex}'))
+                    break
             floor_at_reset[f'e{episode}'] = floor_arr(env, W)
             keyorder_at_reset[f'e{episode}'] = np.asarray(cell_keys(), dtype=np.int32)
             record(t, episode, 0, None, None, False, None, list(obs.values()))
