@@ -8,7 +8,7 @@ import numpy as np
 import golden_compare as G
 
 FIXTURES = ['large8', 'rooms4', 'alltest16', 'maint_rooms', 'eight_puzzle', 'puzzle_dest_crash', 'qquad_doors',
-            'cap_dest81']
+            'cap_dest81', 'pass2_mix', 'cap_maint64']
 EV_FIELDS = ['door_coll', 'door_coll_hi', 'maint_coll', 'respawn_items_value', 'dirt_spawn_value', 'dirt_spawn_valid',
              'dest_reached', 'door_autoclose', 'done_mask', 'crashed', 'crash_reason', 'step', 'episode', 'maint_base']
 

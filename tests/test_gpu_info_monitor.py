@@ -27,11 +27,12 @@ def _acts(torch, seed, B, t, spec, device):
 @pytest.mark.parametrize('cfg,B,kpl', [('alltest16.yaml', 67, 4), ('maint_rooms.yaml', 67, None),
                                        ('eight_puzzle.yaml', 67, None), ('qquad_doors.yaml', 67, None),
                                        ('cap_dest81.yaml', 5, 0)])
-def test_step_columns_equal_torch_columns(cfg, B, kpl):
+def test_step_columns_equal_torch_columns(cfg, B, kpl, min_maint_slot=None):
     """60 steps of explicit Philox-derived actions: every step, the kernel's columns and presence equal
     BatchedFactory.info_columns bit for bit over all envs (crashed envs: the kernel's rows are 0). B = 67 is more
     than one wave of envs and no multiple of the waves per workgroup; alltest16 has several keys per lane in
-    registers, cap_dest81 (81 agents: two-pass row staging) runs the LDS-accumulator kernel."""
+    registers, cap_dest81 (81 agents: two-pass row staging) runs the LDS-accumulator kernel. min_maint_slot: the run
+    must hold a step in which the kernel's column of a maintainer slot >= it is present and non-zero."""
     torch = _need_gpu()
     from mfg_amd.factory import BatchedFactory
     from mfg_amd.monitor import BatchedEnvMonitor
@@ -42,13 +43,18 @@ def test_step_columns_equal_torch_columns(cfg, B, kpl):
     assert mon.monitor.keys_per_lane == want_kpl and (kpl is None or kpl == want_kpl)
     assert mon.monitor.lds_bytes <= 64 * 1024 and 1 <= mon.monitor.waves_per_block <= 4
     mon.reset()
-    bad, live = [], 0
+    bad, live, maint_hit = [], 0, min_maint_slot is None
     for t in range(60):
         at = _acts(torch, 11, B, t, bf.spec, bf.device)
         mon.step(at)
         names, vals, pres = mon.step_columns()
         rnames, rvals, rpres = bf.info_columns(at)
         assert names == rnames
+        if not maint_hit:
+            upper = [k for k, n in enumerate(names) if n.startswith('Maintainer[slot ')
+                     and int(n[len('Maintainer[slot '):n.index(']')]) >= min_maint_slot]
+            assert upper, f'{cfg} has no column of a maintainer slot >= {min_maint_slot}'
+            maint_hit = bool((pres[:, upper] & (vals[:, upper] != 0)).any())
         ok = (bf.ev_misc[:, FLAGS] & CRASH_BIT) == 0
         live += int(ok.sum())
         if not (torch.equal(vals[ok], rvals[ok]) and torch.equal(pres[ok], rpres[ok])):
@@ -56,6 +62,7 @@ def test_step_columns_equal_torch_columns(cfg, B, kpl):
         assert not vals[~ok].any() and not pres[~ok].any()
     mon.close()
     assert not bad and live > 0, (cfg, bad[:10])
+    assert maint_hit, f'{cfg}: no maintainer column of a slot >= {min_maint_slot} was ever present and non-zero'
 
 
 def _stagger_masks(torch, B, device):
