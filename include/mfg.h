@@ -376,7 +376,11 @@ enum { MFG_K_LOGIC = 0, MFG_K_RESETDONE = 1, MFG_K_OBS = 2, MFG_K_REPLAY = 3, MF
        MFG_K_REPLAY_SEL = 6, MFG_K_ACTION_MASK = 7, MFG_K_COUNT = 8 };
 int mfg_profile(mfg_engine* e, int enable);
 int mfg_profile_read(mfg_engine* e, double* total_ms, int64_t* launches, int n);
-/* Snapshots (checkpoint / resume, parity fixtures): whole state buffer device <-> device. */
+/* Snapshots (checkpoint / resume, parity fixtures): whole state buffer device <-> device. A snapshot may be imported,
+ * whole or by rows (a record holds nothing about its index), into any engine of the same spec whose record layout is
+ * equal (mfg_layout: size and offsets), before that engine's first mfg_reset; stepping then continues as in the
+ * exporting engine. One taken under MFG_STEP_DEFER_REPLAY is resumable although its MT state and floor order are not
+ * the reference's: the importing engine's next replay pays the debt it carries. */
 int mfg_export_state(mfg_engine* e, void* dst, void* stream);
 int mfg_import_state(mfg_engine* e, const void* src, void* stream);
 
